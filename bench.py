@@ -9,7 +9,7 @@
 
 One step = one log-prob evaluation (`pdf.forward`) of one batch of synthetic rows: all sub-pdfs, all amortisation MLPs, every layer.
   --workload c3 (default): BASELINE.json's metric configuration `pdf("e4+s2+e4", "gggg+f+gggg")` ("n" of the upstream README = "f"),
-                float32 `value` (+ the float64 rate beside it), 2^20 rows per GPU
+                float32 `value` (+ the float64 rate beside it with --full), 2^20 rows per GPU
   --workload c5: BASELINE configs[4], conditional `pdf("e8+s2", "gggg+v")`, 16 conditioning inputs, AmortizableMLP hidden 128 rank 8, float64
                 ('v' asserts float64 in the reference), 2^19 rows per GPU (= 2^22 over 8)
   --scaling strong (default): the TOTAL batch is fixed (2^20 for c3, 2^22 for c5 -- at N = 1 the one GPU's 2^19 share) and row-sharded over the
@@ -18,13 +18,17 @@ Inputs are synthetic (seeded) and resident in HBM before the timed region; weigh
 (tests/golden/*.npz: reference init with the MLP damping undone, so parameter blocks really vary per row).
 For N > 1 every step all-gathers its log-probs (ONE RCCL all_gather, asynchronous, overlapping the next step; all waited for in the timed region).
 
-Printed JSON line (rank 0): metric/value (whole-job evals/s), ms_per_step, plus
+Printed JSON line (rank 0): metric/value (whole-job evals/s), ms_per_step, dtype and the configuration.  A plain run does only that: set-up,
+preheat, warm-up, the timed steps, and the outputs of the last timed step with --dump-outputs DIR (DIR/<name>.npy, float32 / float64, at most
+64 MB in all: a fixed, seeded row sample of larger outputs).  --full adds everything else the line has carried (measured before or after the
+timed region, never inside it; the timed region then also carries per-kernel HIP events):
   roofline      dominant kernel: SURVEY 8d algorithmic bytes per launch / mean launch time from HIP events recorded in the timed region on
                 the launch stream; `traffic` = HBM bytes per launch from rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE) of this same
                 workload run as child processes before the timed run (or, if rocprofv3 is missing / fails, from the committed profile
                 when the kernel sources are unchanged since it was taken -- otherwise null and `traffic_stale`)
   cpu_baseline  the numpy oracle (kind "port") on this box's host cores (one single-threaded process per core), bounded sample, N = 1 only
   parity        max |d log p| of the timed configuration against the float64 oracle on a 4096-row sample
+  and the float64 leg, rows sweep, other configurations and directions, HIP-graph replay, two-launch path, exchange report (N > 1)
 """
 import os
 
@@ -65,6 +69,7 @@ from benchlib.pmc import (KERNEL_OF, N_SIMDS, SIDE_TABLE_STEPS, WRITE_CAL, commi
 from benchlib.directions import other_direction, train_parity  # noqa: E402,F401
 from benchlib.launcher import dry_run, emit_line, isolate_stdout, launch_ranks  # noqa: E402,F401
 from benchlib.sweeps import other_directions_summary, rows_sweep, shard_with_exchange, side_config  # noqa: E402,F401
+from benchlib.dump import dump_outputs  # noqa: E402
 
 
 # ---------------------------------------------------------------------------------------------- main
@@ -108,7 +113,14 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="exercise launch / rendezvous / row sharding / timing loop / all-gather with a stand-in step on the host (no GPU, no kernels): "
                          "the line carries \"dry_run\": true and no throughput claim.  For the CPU tests (JF_BENCH_BACKEND=gloo)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: CPU baseline, PMC traffic passes, oracle parity, float64 leg, determinism repeats, per-kernel tables and "
+                         "rooflines, rows sweep, other configurations and directions, HIP-graph replay, two-launch path, exchange report (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.pipeline_depth is None:
         args.pipeline_depth = 3
     if args.train:
@@ -145,7 +157,7 @@ def main():
     cpu = None
     traffic = None
     strided = None
-    if rank == 0 and world == 1 and not args.pmc_child:
+    if rank == 0 and world == 1 and not args.pmc_child and args.full:
         if not args.no_cpu_baseline:
             cpu = cpu_baseline(args.workload)                        # before the GPU is touched (fork safety)
             # untiled full-size parity: 2^16 rows strided across the whole batch through the float64 oracle (a few seconds on the box's cores)
@@ -160,7 +172,7 @@ def main():
             del xs64, cs64
         if not args.no_pmc:
             traffic = measure_traffic(args.workload, B, not args.no_fuse)   # child processes; this process has not touched the GPU yet
-    if traffic is None:
+    if traffic is None and args.full:
         traffic = committed_traffic()
 
     import torch
@@ -194,7 +206,7 @@ def main():
     x64, c64 = make_inputs(args.workload, B, W["seed"] + rank)
     dtypes = {"f32": torch.float32, "f64": torch.float64}
     main_dt = W["dtype"]
-    order = [main_dt] + (["f64"] if (main_dt == "f32" and not args.pmc_child) else [])
+    order = [main_dt] + (["f64"] if (main_dt == "f32" and not args.pmc_child and args.full) else [])
 
     if args.pmc_child:                                   # a few untimed steps for the PMC passes
         if args.pmc_dtype:
@@ -216,6 +228,7 @@ def main():
     two_launch = None
     graph_replay = None
     side_table = None
+    dumped = None
     for dname in order:
         dtype = dtypes[dname]
         pdf = helpers.build_product(fx, dtype, dev)
@@ -227,6 +240,8 @@ def main():
         # N > 1: the per-row log-probs of every step are all-gathered (RCCL), asynchronously, while the next step computes
         gather = parallel.PipelinedGather(B, dtype, dev, group_steps=args.gather_steps) if (multi and total_rows % world == 0) else None
         last = {}
+        # --dump-outputs: the last timed step (call warmup + steps after the preheat) keeps all its outputs; every other step is untouched
+        calls = {"n": 0, "keep_at": args.warmup + args.steps if (args.dump_outputs and dname == main_dt) else -1}
 
         # consecutive steps are independent batches: they alternate between `--pipeline-depth` streams, each through its own recorded plan, so
         # the idle tail of one step's last round of workgroups is filled by the head of the next step (DESIGN "small shards"); every step's
@@ -240,6 +255,7 @@ def main():
                 print("bench: pipelined_forward failed (%s); continuing on one stream" % pipeline_error, file=sys.stderr)
 
         def step():
+            calls["n"] += 1
             if pipe is not None:
                 if gather is not None:
                     # the step writes its log-probs straight into the stage of the next exchange; every --gather-steps-th step the exchange is
@@ -250,10 +266,16 @@ def main():
                     t = pipe.submit(x, c)
                 # (the log-probs are what the step is for: the other two outputs -- 44 MB at 2^20 rows -- go back to the allocator at once, as
                 #  they do for a caller that does not hold on to them; holding three steps' worth of them alive rotates the writes over ~190 MB)
+                if calls["n"] == calls["keep_at"]:
+                    last["outputs"] = t.outputs
                 t.outputs = t.outputs[:1]
                 last["pending"] = t
                 return
-            logp = pdf(x, conditional_input=c)[0]
+            out = pdf(x, conditional_input=c)
+            if calls["n"] == calls["keep_at"]:
+                last["outputs"] = out
+            logp = out[0]
+            del out
             if gather is not None:
                 gather.submit(logp)
             last["logp"] = logp
@@ -269,7 +291,8 @@ def main():
 
         # HIP events around the kernels of every 4th replay of a plan (the instrumentation costs ~2 % of a 2^20-row step and ~7 % of a 2^17-row
         # shard step when every replay carries it; the default 50 steps give a dozen timed replays per kernel; totals are scaled to all replays)
-        timer = _hip.KernelTimer(plan_every=int(os.environ.get("JF_BENCH_TIMER_EVERY", "4"))) if dname == main_dt else None
+        # (--full only: a plain run times the steps without instrumentation)
+        timer = _hip.KernelTimer(plan_every=int(os.environ.get("JF_BENCH_TIMER_EVERY", "4"))) if (dname == main_dt and args.full) else None
         # bring the chip to its sustained clocks first: a 20-step region of 0.8 ms steps starts ~20 ms after the GPU sat idle (inputs were being
         # generated on the host), inside the power-management ramp -- the same plan measured 0.86 ms per step there and 0.78 ms once it had run for
         # 50 ms.  Untimed, before the contract's own W warm-up steps; reported in the line (`preheat_ms`).
@@ -280,9 +303,14 @@ def main():
                     step()
                 torch.cuda.synchronize(dev)
             finish()
+        calls["n"] = 0
         tinfo = {}
         dt = parallel.timed_steps(step, args.steps, args.warmup, finish=finish, device=dev, timer=timer, info=tinfo)
-        if timer is None and rank == 0:
+        if "outputs" in last:
+            # what the caller of the timed path received from its last step (finish() has made this stream wait for it)
+            dumped = dump_outputs(args.dump_outputs, dict(zip(("log_prob", "log_prob_base", "base_pos"), last.pop("outputs"))),
+                                  rank=rank, world=world)
+        if dname != main_dt and rank == 0:
             # the secondary (float64) leg: per-kernel HIP-event times of three more EAGER steps, outside its timed region.  Two untimed eager steps
             # first: the timed region ran recorded plans (merged side kernels), so an eager step is the first launch of the stand-alone kernels in
             # this process -- code-object load and attribute calls landed between the events of that first launch (round 5's line read 20 ms for
@@ -303,13 +331,14 @@ def main():
         if gather is not None:
             full = gather.wait()
             torch.cuda.synchronize(dev)
-            mine = gather.last_block(rank)
-            gather_info = {"path": gather.path, "direct_error": gather.direct_error, "steps_per_collective": gather.k,
-                           "own_block_correct": bool(((mine == logp) | (mine.isnan() & logp.isnan())).all())}
+            gather_info = {"path": gather.path, "direct_error": gather.direct_error, "steps_per_collective": gather.k}
+            if args.full:
+                mine = gather.last_block(rank)
+                gather_info["own_block_correct"] = bool(((mine == logp) | (mine.isnan() & logp.isnan())).all())
             gather.close()
         # parity of what was just timed, against the float64 oracle (rank 0, 4096 rows)
         err = None
-        if rank == 0:
+        if rank == 0 and args.full:
             n_chk = min(4096, B)
             o = helpers.build_oracle(fx).forward(x64[:n_chk], None if c64 is None else c64[:n_chk])[0]
             err = float(np.max(np.abs(logp[:n_chk].double().cpu().numpy() - o)))
@@ -322,7 +351,7 @@ def main():
                        "finiteness_mismatches": int((np.isfinite(got) != fin).sum()), "oracle_seconds": round(strided["oracle_s"], 2)}
         # determinism of what was just timed (outside the timed region): the same step again, compared bit for bit over ALL rows -- the check that
         # exposes rare wrong row groups which a 4096-row oracle sample cannot see
-        repeats, identical = 3, True
+        repeats, identical = (3, True) if args.full else (0, None)
         for _ in range(repeats):
             again = pdf(x, conditional_input=c)[0]
             identical = identical and bool(((again == logp) | (again.isnan() & logp.isnan())).all())
@@ -330,7 +359,7 @@ def main():
         results[dname] = dict(dt=dt, evals_per_s=total_rows * args.steps / dt, ms_per_step=1e3 * dt / args.steps, err=err, identical=identical, repeats=repeats,
                               untiled=untiled, gather=gather_info, host_issue_ms=1e3 * tinfo.get("host_issue_s", 0.0) / args.steps,
                               rank_ms=parallel.rank_time_stats(tinfo, args.steps), ranks_in_timing=tinfo.get("n_ranks_seen"))
-        if rank == 0 and world == 1 and dname == main_dt and not args.no_sweep:
+        if rank == 0 and world == 1 and dname == main_dt and args.full and not args.no_sweep:
             results[dname]["rows_sweep"] = rows_sweep(pdf, x, c, depth=args.pipeline_depth if pipe is not None else 1)
         if timer is not None:
             kernel_table = timer.summary()
@@ -372,13 +401,43 @@ def main():
         del pdf, x, c
 
     # N > 1: who held how many rows, and what one stand-alone all-gather of the log-probs costs (outside the timed region; every rank)
-    exchange = parallel.gather_report(B, dtypes[main_dt], dev) if multi else None
-    if exchange is not None and results[main_dt].get("gather"):
-        exchange.update(results[main_dt]["gather"])
+    exchange = parallel.gather_report(B, dtypes[main_dt], dev) if (multi and args.full) else None
+    if results[main_dt].get("gather"):
+        exchange = dict(exchange or {}, **results[main_dt]["gather"])
     if multi:
         dist.barrier()
     if rank == 0:
         rm = results[main_dt]
+        line = {
+            "metric": W["metric"],
+            "value": rm["evals_per_s"], "unit": "log-prob evals/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": rm["ms_per_step"], "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": main_dt,
+            "data": "synthetic (seeded; weights = frozen golden-fixture state_dict)",
+            "config": {"workload": 'pdf("%s","%s") log-prob, %s, %d rows %s' % (W["defs"][0], W["defs"][1], W["desc"],
+                                                                                  B if args.scaling == "weak" else total_rows,
+                                                                                  "per GPU" if args.scaling == "weak" else "in total, row-sharded"),
+                       "batch_per_gpu": B, "total_rows": total_rows, "parallelism": "rows sharded over %d GPU(s)" % world},
+            "n_ranks_seen": n_ranks_seen, "collective_backend": backend_name, "exchange": exchange,
+            "forced_collectives": bool(multi and world == 1),
+            # every rank's own clock between the two fences of the timed region (ms per step): `ms_per_step` is the slowest rank's; a straggler shows here
+            "rank_ms_per_step": rm["rank_ms"], "ranks_in_timing": rm["ranks_in_timing"],
+            "hw_queues": {"GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES"), "set_by": "bench.py / jammy_flows_amd.parallel at import (%s)" % parallel.HW_QUEUES_STATE},
+            "host_issue_ms_per_step": rm["host_issue_ms"],
+            "preheat_ms": args.preheat_ms,
+            "step_issue": ("recorded step plan: one ctypes call per step (jf_plan_launch)" + (
+                "; consecutive steps alternate between %d streams (pdf.pipelined_forward)" % args.pipeline_depth if args.pipeline_depth > 1 else ""))
+            if not args.no_plan else "eager: one ctypes call per launch",
+            "pipeline_depth": 1 if (args.no_plan or pipeline_error) else args.pipeline_depth, "pipeline_error": pipeline_error,
+            "full": args.full,
+        }
+        if dumped is not None:
+            line["dump_outputs"] = dumped
+        if args.t1_ms is not None and world > 1:
+            tn = rm["ms_per_step"]
+            line["scaling_efficiency_vs_t1"] = {"t1_ms": args.t1_ms, "tN_ms": tn, "n_gpus": world, "scaling": args.scaling,
+                                                "efficiency": (args.t1_ms / (world * tn)) if args.scaling == "strong" else (args.t1_ms / tn),
+                                                "definition": "strong: T_1 / (N T_N) at fixed total batch; weak: T_1 / T_N at fixed per-GPU batch (BASELINE.md section 3)"}
+    if rank == 0 and args.full:
         s = 4 if main_dt == "f32" else 8
         # ---- roofline of the dominant kernel.  SURVEY 8d: the conditional blocks are priced against HBM on the MATERIALISED accounting
         # (MLP reads its inputs and writes the block, the flow reads the block); a fused kernel moves almost none of it and may exceed 100 %.
@@ -488,21 +547,7 @@ def main():
             # the same durations at each kernel's share of the chip's time (they add up to the step time)
             roofline["all_kernels_effective_ms_per_step"] = {"%s[%s]" % k: round(v["total_ms"] / args.steps / concurrency, 4)
                                                              for k, v in sorted(kernel_table.items())}
-        line = {
-            "metric": W["metric"],
-            "value": rm["evals_per_s"], "unit": "log-prob evals/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": rm["ms_per_step"], "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": main_dt,
-            "data": "synthetic (seeded; weights = frozen golden-fixture state_dict)",
-            "config": {"workload": 'pdf("%s","%s") log-prob, %s, %d rows %s' % (W["defs"][0], W["defs"][1], W["desc"],
-                                                                                  B if args.scaling == "weak" else total_rows,
-                                                                                  "per GPU" if args.scaling == "weak" else "in total, row-sharded"),
-                       "batch_per_gpu": B, "total_rows": total_rows, "parallelism": "rows sharded over %d GPU(s)" % world},
-            "n_ranks_seen": n_ranks_seen, "collective_backend": backend_name, "exchange": exchange,
-            "forced_collectives": bool(multi and world == 1),
-            # every rank's own clock between the two fences of the timed region (ms per step): `ms_per_step` is the slowest rank's; a straggler shows here
-            "rank_ms_per_step": rm["rank_ms"], "ranks_in_timing": rm["ranks_in_timing"],
-            "hw_queues": {"GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES"), "set_by": "bench.py / jammy_flows_amd.parallel at import (%s)" % parallel.HW_QUEUES_STATE},
-            "host_issue_ms_per_step": rm["host_issue_ms"],
+        line.update({
             "parity": {"max_abs_dlogp_vs_f64_oracle": rm["err"], "bar": 1e-2 if main_dt == "f32" else 1e-4, "rows_checked": min(4096, B),
                        "repeat_launches_bit_identical": rm["identical"], "repeat_launches": rm["repeats"], "repeat_rows_compared": B,
                        "untiled_full_size": rm["untiled"]},
@@ -510,19 +555,9 @@ def main():
                            "(f32 accumulation; measured deviation from the float64 oracle in `parity`, bar 1e-2 -- the reference's own fp32-vs-fp64 "
                            "agreement is ~3e-5); `cpu_baseline` is the float64 oracle; the like-for-like float64 rate is under `float64`")
                           if main_dt == "f32" else None,
-            "preheat_ms": args.preheat_ms,
-            "step_issue": ("recorded step plan: one ctypes call per step (jf_plan_launch)" + (
-                "; consecutive steps alternate between %d streams (pdf.pipelined_forward)" % args.pipeline_depth if args.pipeline_depth > 1 else ""))
-            if not args.no_plan else "eager: one ctypes call per launch",
-            "pipeline_depth": 1 if (args.no_plan or pipeline_error) else args.pipeline_depth, "pipeline_error": pipeline_error,
             "roofline": roofline,
             "cpu_baseline": cpu,
-        }
-        if args.t1_ms is not None and world > 1:
-            tn = rm["ms_per_step"]
-            line["scaling_efficiency_vs_t1"] = {"t1_ms": args.t1_ms, "tN_ms": tn, "n_gpus": world, "scaling": args.scaling,
-                                                "efficiency": (args.t1_ms / (world * tn)) if args.scaling == "strong" else (args.t1_ms / tn),
-                                                "definition": "strong: T_1 / (N T_N) at fixed total batch; weak: T_1 / T_N at fixed per-GPU batch (BASELINE.md section 3)"}
+        })
         if "f64" in results and main_dt != "f64":
             r64 = results["f64"]
             line["float64"] = {"value": r64["evals_per_s"], "ms_per_step": r64["ms_per_step"], "max_abs_dlogp_vs_f64_oracle": r64["err"], "bar": 1e-4,
@@ -632,6 +667,7 @@ def main():
                 blk["gf_chain_per_sample"] = {"bound": "hbm", "achieved": gb, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": gb / HBM_PEAK_GBS,
                                               "mean_launch_ms": gf["mean_ms"], "algorithmic_bytes_per_launch": 4 * 558 * B}
             line["two_launch_path"] = blk
+    if rank == 0:
         emit_line(line)
     if multi:
         dist.destroy_process_group()

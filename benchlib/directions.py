@@ -17,6 +17,7 @@ from .workloads import ROOT, BENCH_PY, WORKLOADS, make_inputs
 from .cpu import cpu_baseline_sampling
 from .pmc import kernel_accounting, traffic_of, committed_traffic
 from .launcher import emit_line
+from .dump import dump_outputs
 
 def train_parity(name, dtype, dev, torch_adam):
     """The training step's parity: the gradient of -mean(log p) at the golden fixture's rows against the REAL reference's autograd
@@ -167,6 +168,10 @@ def other_direction(args, W, rank, local_rank, world):
     # the K timed steps run WITHOUT the per-launch HIP events (two event records per launch cost the host 10-20 us, which a training step of
     # ~20-30 launches feels); the per-kernel table is a second pass of the same steps right after the timed region
     dt = parallel.timed_steps(step, args.steps, args.warmup, finish=finish, device=dev, timer=None)
+    dumped = None
+    if args.dump_outputs:                                      # what the last timed step returned, before anything else runs the step again
+        outs = {"samples": last["x"], "log_prob": last["lp"]} if direction == "sample" else {"loss": last["loss"]}
+        dumped = dump_outputs(args.dump_outputs, outs, rank=rank, world=world)
     timer = _hip.KernelTimer()
     n_table = min(args.steps, 10)
     with timer:
@@ -280,6 +285,8 @@ def other_direction(args, W, rank, local_rank, world):
         if direction == "train":
             line["cpu_baseline_note"] = "the oracle restates the forward arithmetic only: no CPU training baseline travels to the GPU box"
         line.update(extra)
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         emit_line(line)
     if multi:
         dist.destroy_process_group()

@@ -69,7 +69,7 @@ def shard_with_exchange(workload, rows, gather_steps, full_ms, exchange=True):
     timed region) runs `bench.py --batch rows`; exchange: through the N > 1 path, with a process group of ONE rank (JF_FORCE_COLLECTIVES=1), so
     every step hands its log-probs to RCCL"""
     cmd = [sys.executable, BENCH_PY, "--workload", workload, "--batch", str(rows), "--gather-steps", str(gather_steps), "--no-cpu-baseline",
-           "--no-pmc", "--no-sweep", "--steps", "400", "--warmup", "20"]
+           "--no-pmc", "--no-sweep", "--full", "--steps", "400", "--warmup", "20"]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     env.pop("JF_FORCE_COLLECTIVES", None)
     if exchange:

@@ -5,8 +5,8 @@ tag=$1; shift
 out=gpurun_out/prof_$tag
 mkdir -p $out
 export TMPDIR=/tmp
-# the stats pass runs the DEFAULT bench command (the default number of timed steps, clocks ramped) so that its per-kernel averages are the ones the bench line reports
-rocprofv3 --kernel-trace --stats -d $out/stats -- python3 bench.py --no-pmc --no-sweep "$@" > $out/stats.log 2>&1     # (--no-sweep: only full-size launches, so the averages are the timed step's)
+# the stats pass runs the --full bench command (the default number of timed steps, clocks ramped) so that its per-kernel averages are the ones the bench line reports
+rocprofv3 --kernel-trace --stats -d $out/stats -- python3 bench.py --full --no-pmc --no-sweep "$@" > $out/stats.log 2>&1     # (--no-sweep: only full-size launches, so the averages are the timed step's)
 rocprofv3 --pmc FETCH_SIZE -d $out/fetch -- python3 bench.py --pmc-child "$@" > $out/fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE -d $out/write -- python3 bench.py --pmc-child "$@" > $out/write.log 2>&1
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_LDS -d $out/sq1 -- python3 bench.py --pmc-child "$@" > $out/sq1.log 2>&1
