@@ -49,18 +49,33 @@ constexpr float CS_M_SCALED = 60.0f;
 // sums (optional): the normalised linear-space cdf, sf, pdf and 1 / N -- what the adjoint kernel's linear-space path starts from (a pdf that
 // underflows there sends the row's wave to the log-space path)
 struct CsSums { float C, S, P, invN; };
-__device__ __forceinline__ MixQ<float> cs_mixture(const float (&P)[CS_SLOTS], const CsLayer& o, float x, bool live, CsSums* sums = nullptr) {
+constexpr float CS_LOG2E = 1.44269504088896340736f, CS_LN2 = 0.69314718055994530942f, CS_LNLN2 = -0.36651292058166432701f;   // ln(ln 2)
+__device__ __forceinline__ float cs_exp2(float x) { return __builtin_amdgcn_exp2f(x); }             // v_exp_f32
+__device__ __forceinline__ float cs_log2(float x) { return __builtin_amdgcn_logf(x); }              // v_log_f32 (normal-range inputs only)
+// a wave-uniform value made from vector operands (an LDS word, products of kernel arguments) -> a scalar register: one vector register
+// fewer for the layer's constants at the register limit of the fused block
+__device__ __forceinline__ float cs_uniform(float x) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x))); }
+// A: the lane's RAW parameter registers, parameter = A * pscale (pscale a power of two: the f16-pair arithmetic's 2^-(e + 14), else 1).  The
+// scale is taken inside instructions the arithmetic has anyway (the mean in the fma of x - mu, the log-width / log-weight in the one multiply
+// in front of their v_exp) instead of a multiply per register (exact either way).  Widths and distances are carried in log2 units --
+// iw2 = log2(e) / w, u2 = log2(e) (x - mu) / w -- so that the sigmoid's v_exp takes -u2 as it is: log2(e) rides in the regulation's
+// fma (1/wmax + e^-p) log2(e) and leaves through one ln 2 in front of the pdf's logarithm.  Sums start from the first component (a
+// sum started at +0.f costs an add: x + 0 is not x for x = -0).
+__device__ __forceinline__ MixQ<float> cs_mixture(const float (&A)[CS_SLOTS], const CsLayer& o, float pscale, float x, bool live,
+                                                  CsSums* sums = nullptr) {
     using Mf = M<float>;
+    const float ke = cs_uniform(-pscale * CS_LOG2E);               // e^{-p} = 2^{A ke}
+    const float iwmax2 = cs_uniform(o.inv_wmax * CS_LOG2E), wmin2 = cs_uniform(o.wmin * CS_LN2);
     float iw[CS_K], wk[CS_K], u[CS_K];
-    float m = INFINITY, Nn = 0.f;
+    float m, Nn;
 #pragma unroll
     for (int k = 0; k < CS_K; ++k) {
-        const float ae = o.inv_wmax + Mf::exp_fast(-P[CS_SLOT_LW + k]);
-        iw[k] = ae * Mf::rcp(o.wmin * ae + 1.0f);
-        wk[k] = o.nmin + o.nmax * Mf::rcp(1.0f + Mf::exp_fast(-P[CS_SLOT_LN + k]));
-        u[k] = (x - P[CS_SLOT_MEAN + k]) * iw[k];
-        m = fminf(m, fabsf(u[k]));
-        Nn += wk[k];
+        const float ae = fmaf(cs_exp2(A[CS_SLOT_LW + k] * ke), CS_LOG2E, iwmax2);               // log2(e) (1/wmax + e^{-p})
+        iw[k] = ae * Mf::rcp(fmaf(wmin2, ae, 1.0f));
+        wk[k] = o.nmin + o.nmax * Mf::rcp(1.0f + cs_exp2(A[CS_SLOT_LN + k] * ke));
+        u[k] = fmaf(-A[CS_SLOT_MEAN + k], pscale, x) * iw[k];
+        m = k ? fminf(m, fabsf(u[k])) : fabsf(u[k]);
+        Nn = k ? Nn + wk[k] : wk[k];
     }
     const float inv = Mf::rcp(Nn);
     MixQ<float> q;
@@ -68,44 +83,45 @@ __device__ __forceinline__ MixQ<float> cs_mixture(const float (&P)[CS_SLOTS], co
         // differently: a row's bits depended on the 15 rows it shared a wave with -- 12 % of the rows of the SURVEY inputs differed between a
         // 2^20-row batch and the same rows evaluated alone, tests/test_gpu_fullsize.py.  The scaled sums are taken per LANE now; 3 % of the
         // calls see a far lane and pay for both forms.)
-        float C = 0.f, S = 0.f, Pd = 0.f;
+        float C, S, Pd;                                            // Pd in log2 units (log2(e) x the pdf's sum)
 #pragma unroll
         for (int k = 0; k < CS_K; ++k) {
             // s = sigma(u) = 1 / (1 + e^{-u}), sigma(-u) = e^{-u} s: no |u|, no compare, no selects (jf_gfb.h: gfb_mix_sums).  The exponent is
             // capped so that e^{-u} stays finite (87 < ln FLT_MAX): such a lane is `far` (m > CS_M_SCALED) and takes the scaled sums below
-            const float t = Mf::exp_fast(fminf(-u[k], 87.0f));
+            const float t = cs_exp2(fminf(-u[k], 87.0f * CS_LOG2E));
             const float s = Mf::rcp(1.0f + t);
             const float ts = t * s;
-            C += wk[k] * s;
-            S += wk[k] * ts;
-            Pd += wk[k] * s * ts * iw[k];
+            const float ws = wk[k] * s;
+            C = k ? C + ws : ws;
+            S = k ? fmaf(wk[k], ts, S) : wk[k] * ts;
+            Pd = k ? fmaf(ws * ts, iw[k], Pd) : ws * ts * iw[k];
         }
         C *= inv; S *= inv; Pd *= inv;
-        q.lc = Mf::log_fast(C); q.ls = Mf::log_fast(S); q.lp = Mf::log_fast(Pd);
+        q.lc = Mf::log_fast(C); q.ls = Mf::log_fast(S); q.lp = fmaf(cs_log2(Pd), CS_LN2, CS_LNLN2);     // ln(Pd ln 2)
         q.cdf = C; q.sf = S;
-        if (sums) *sums = CsSums{C, S, Pd, inv};
+        if (sums) *sums = CsSums{C, S, Pd * CS_LN2, inv};
     }
-    const bool far = m > CS_M_SCALED;                              // this lane's target is far from every component: plain sums underflow
+    const bool far = m > CS_M_SCALED * CS_LOG2E;                   // this lane's target is far from every component: plain sums underflow
     if (!__any(live && far)) return q;                             // wave-uniform branch
-    const float em = Mf::exp_fast(-m);                             // may underflow to 0: the unscaled parts then stand alone
-    float Cu = 0.f, Cs = 0.f, Su = 0.f, Ss = 0.f, Ps = 0.f;
+    const float em = cs_exp2(-m);                                  // may underflow to 0: the unscaled parts then stand alone
+    float Cu = 0.f, Cs = 0.f, Su = 0.f, Ss = 0.f, Ps;
 #pragma unroll
     for (int k = 0; k < CS_K; ++k) {
-        const float t = Mf::exp_fast(m - fabsf(u[k]));
+        const float t = cs_exp2(m - fabsf(u[k]));
         const float hi = Mf::rcp(1.0f + t * em);
         const float c1 = wk[k] * hi, c2 = c1 * t;
         if (u[k] >= 0.f) { Cu += c1; Ss += c2; }
         else { Su += c1; Cs += c2; }
-        Ps += c2 * hi * iw[k];
+        Ps = k ? fmaf(c2 * hi, iw[k], Ps) : c2 * hi * iw[k];
     }
     Cu *= inv; Cs *= inv; Su *= inv; Ss *= inv; Ps *= inv;
     if (far) {
         q.cdf = Cu + em * Cs;
         q.sf = Su + em * Ss;
-        q.lc = Cu > 0.f ? Mf::log_fast(q.cdf) : Mf::log_fast(Cs) - m;
-        q.ls = Su > 0.f ? Mf::log_fast(q.sf) : Mf::log_fast(Ss) - m;
-        q.lp = Mf::log_fast(Ps) - m;
-        if (sums) *sums = CsSums{q.cdf, q.sf, Ps * em, inv};
+        q.lc = Cu > 0.f ? Mf::log_fast(q.cdf) : CS_LN2 * (cs_log2(Cs) - m);
+        q.ls = Su > 0.f ? Mf::log_fast(q.sf) : CS_LN2 * (cs_log2(Ss) - m);
+        q.lp = fmaf(cs_log2(Ps) - m, CS_LN2, CS_LNLN2);
+        if (sums) *sums = CsSums{q.cdf, q.sf, Ps * CS_LN2 * em, inv};
     }
     return q;
 }

@@ -111,6 +111,20 @@ template <typename Op> __device__ __forceinline__ float cs_rreduce(float v, Op o
     return op(c, e);
 }
 __device__ __forceinline__ float cs_rsum(float v) { return cs_rreduce(v, [](float a, float b) { return a + b; }); }
+// the row sums of four values at once, f applied to each sum: a reduce-scatter over the two swaps (distinct operands: after
+// permlane16_swap(x, y) x = {x0, y0, x2, y2} and y = {x1, y1, x3, y3} by 16-lane row, after permlane32_swap(x, y) x = {x0, x1, y0, y1} and
+// y = {x2, x3, y2, y3}) leaves sum i in row i, where f runs once, then an all-gather.  6 swaps, 3 adds and 3 copies where four cs_rsum
+// take 8, 8 and 8; each sum is added in cs_rsum's order (rows 0 + 1, 2 + 3, then the two), so it carries the same bits
+template <typename F> __device__ __forceinline__ void cs_rsum4(float a, float b, float c, float d, F f, float (&out)[4]) {
+    asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\tv_permlane16_swap_b32 %2, %3" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
+    float ab = a + b, cd = c + d;                                  // {a01, b01, a23, b23}, {c01, d01, c23, d23}
+    asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(ab), "+v"(cd));
+    float t = f(ab + cd), t2 = t;                                  // row i: f(sum i)
+    asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(t), "+v"(t2));         // {A, B, A, B}, {C, D, C, D}
+    float t1 = t, t3 = t2;
+    asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\tv_permlane16_swap_b32 %2, %3" : "+v"(t), "+v"(t1), "+v"(t2), "+v"(t3));
+    out[0] = t; out[1] = t1; out[2] = t2; out[3] = t3;
+}
 __device__ __forceinline__ float cs_rmax(float v) { return cs_rreduce(v, [](float a, float b) { return fmaxf(a, b); }); }
 
 static inline bool cs_layer_supported(const jf_gf_layer& h, int D) {

@@ -93,6 +93,7 @@ __device__ __forceinline__ void cond_gf_split_body(const CsArgs& a, const int bl
     for (int li = 0; li < a.n_layers; ++li) {
         const int l = FWD ? li : a.n_layers - 1 - li;
         float P[RG][CS_SLOTS];
+        float pscale = 1.0f;                                       // log-prob direction: parameter = P * pscale (see below)
 #pragma unroll
         for (int c = 0; c < CS_CPL; ++c, ++chunk) {
             if (chunk + 1 < n_chunks) dma(chunk + 1);              // in flight while this chunk is multiplied
@@ -152,12 +153,15 @@ __device__ __forceinline__ void cond_gf_split_body(const CsArgs& a, const int bl
                         for (int r = 0; r < 4; ++r) P[g][4 * (c * CS_CT + t) + r] = acc[g][t][r];
             } else {
                 const float inv = Bs[CS_B_BYTES / 4];                // 2^-(e + 14): the scales of W2 and h undone (exact)
+                // the log-prob direction keeps the accumulators as they are and takes the scale inside the flow's own arithmetic (cs_mixture;
+                // a Householder reflection does not see the length of v): 35 multiplies per row group and layer fewer
+                if constexpr (!FWD) pscale = cs_uniform(inv);
 #pragma unroll
                 for (int g = 0; g < RG; ++g)
 #pragma unroll
                     for (int t = 0; t < CS_CT; ++t)
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) P[g][4 * (c * CS_CT + t) + r] = acc[g][t][r] * inv;
+                        for (int r = 0; r < 4; ++r) P[g][4 * (c * CS_CT + t) + r] = FWD ? acc[g][t][r] * inv : acc[g][t][r];
             }
             if (c + 1 < CS_CPL) landed();                          // next chunk in place, every wave has read this one
         }
@@ -166,17 +170,19 @@ __device__ __forceinline__ void cond_gf_split_body(const CsArgs& a, const int bl
 #pragma unroll
         for (int g = 0; g < RG; ++g) {
             if constexpr (!FWD) {
-                float xg = x[g] - P[g][CS_SLOT_OFF];               // euclidean_base.py:40-45 (zero column when the layer models no offset)
+                float xg = fmaf(-P[g][CS_SLOT_OFF], pscale, x[g]);  // euclidean_base.py:40-45 (zero column when the layer models no offset)
+                // x <- Q^T x (gaussianization_flow.py:1038), H_i = I - 2 v v^T / |v|^2.  The four |v_i|^2 do not depend on x: one batched
+                // reduction, and 2 / |v_i|^2 taken once per row before the gather
+                // (a lane past the row's D coordinates holds v = 0: its columns of W2 and b2 are packed as zeros)
+                const float* v = &P[g][CS_SLOT_ROT];
+                float r2[CS_HH];
+                cs_rsum4(v[0] * v[0], v[1] * v[1], v[2] * v[2], v[3] * v[3], [](float n2) { return 2.0f * M<float>::rcp(n2); }, r2);
 #pragma unroll
                 for (int i = 0; i < CS_HH; ++i) {
-                    if (i < o.hh) {                                // x <- Q^T x (gaussianization_flow.py:1038), H_i = I - 2 v v^T / |v|^2
-                        const float v = live ? P[g][CS_SLOT_ROT + i] : 0.f;
-                        const float n2 = cs_rsum(v * v), dot = cs_rsum(v * xg);
-                        xg -= 2.0f * dot * M<float>::rcp(n2) * v;
-                    }
+                    if (i < o.hh) xg -= cs_rsum(v[i] * xg) * r2[i] * v[i];
                 }
                 CsSums sums;
-                const MixQ<float> q = cs_mixture(P[g], o, xg, live, SAVE ? &sums : nullptr);
+                const MixQ<float> q = cs_mixture(P[g], o, pscale, xg, live, SAVE ? &sums : nullptr);
                 if constexpr (SAVE) {
                     {   // (row number re-derived from the lane index: see the epilogue)
                         int t2 = tid;

@@ -109,7 +109,8 @@ template <typename T> struct MixQ { T lc, ls, lp, cdf, sf; };   // log cdf, log 
 // ----------------------------------------------------------------------------------------------------------
 template <typename T> struct Pade { T F2, F2mF; };   // F2 = sqrt(F^2 - ln_fac/a),  F2mF = F2 - F (cancellation-free)
 
-template <typename T> __device__ __forceinline__ Pade<T> pade_terms(const MixQ<T>& q) {
+// TAIL: the caller's lanes all sit in a tail (min(cdf, sf) <= PADE_BOUND, far below the centre window), so the centre form cannot be taken
+template <typename T, bool TAIL = false> __device__ __forceinline__ Pade<T> pade_terms(const MixQ<T>& q) {
     const T a = T(PADE_A);
     const T c = T(2.0 / (3.14159265358979323846 * PADE_A));
     // ln(4 cdf sf) = log1p(-(sf-cdf)^2) in the centre (no cancellation), log-space sum in the tails
@@ -122,7 +123,7 @@ template <typename T> __device__ __forceinline__ Pade<T> pade_terms(const MixQ<T
         // waves mix centre and tail rows -- both sides of the region branch run there.)
         const bool centre = M<T>::min(q.cdf, q.sf) > T(0.01);
         T ln_fac = q.lc + q.ls + T(1.38629436111989061883);
-        if (__any(centre)) {
+        if (!TAIL && __any(centre)) {
             const T l1p = M<T>::log1p(-dlt * dlt);
             ln_fac = centre ? l1p : ln_fac;
         }
@@ -132,7 +133,7 @@ template <typename T> __device__ __forceinline__ Pade<T> pade_terms(const MixQ<T
         p.F2mF = F > T(0) ? rad * M<T>::rcp(p.F2 + F) : p.F2 - F;
         return p;
     }
-    const T ln_fac = (M<T>::min(q.cdf, q.sf) > T(0.01)) ? M<T>::log1p(-dlt * dlt) : q.lc + q.ls + T(1.38629436111989061883);
+    const T ln_fac = (!TAIL && M<T>::min(q.cdf, q.sf) > T(0.01)) ? M<T>::log1p(-dlt * dlt) : q.lc + q.ls + T(1.38629436111989061883);
     const T F = ln_fac * T(0.5) + c;
     const T rad = -ln_fac / a;
     p.F2 = M<T>::sqrt(F * F + rad);
@@ -214,7 +215,7 @@ template <typename T> __device__ __forceinline__ T gf_inverse_cdf(int inv_type, 
             logd = T(-0.5) * M<T>::log(T(-2) * lsum) - lsum + q.lp;
         }
     } else {
-        const Pade<T> p = pade_terms(q);
+        const Pade<T> p = pade_terms<T, true>(q);                 // (no log1p in the code: ~120 instructions per inlined copy in float32)
         tot = pade_value(p);
         logd = pade_logderiv(p, q) + q.lp;
     }
