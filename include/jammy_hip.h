@@ -97,7 +97,8 @@ typedef struct jf_gf_layer {
  * layer (spline_fns.py:13-19, 252-258) -- the integer output the bit-exact parity tests compare. */
 /* LDS bytes one launch of this chain needs in the log-prob / sampling direction (jf_gf_chain_lds_bytes_*) and in the backward direction
  * (jf_gf_chain_inv_bwd_lds_bytes_*), or a negative JF_ERR_* (JF_ERR_UNSUPPORTED: more than the 160 KB of a CU).  param_batch_is_one: the
- * broadcast regime.  The host cuts chains of wide layers (D up to 32: groups of 16 / 32 lanes per row) into launches that fit. */
+ * broadcast regime.  The host cuts chains of wide layers (D up to 32: groups of 16 / 32 lanes per row) into launches that fit.  A broadcast
+ * backward whose LDS tables and accumulators would exceed a CU accumulates in the partial rows in global memory instead and reports 0 bytes. */
 int64_t jf_gf_chain_lds_bytes_f32(int32_t D, int32_t n_layers, const jf_gf_layer* layers, int32_t param_batch_is_one);
 int64_t jf_gf_chain_lds_bytes_f64(int32_t D, int32_t n_layers, const jf_gf_layer* layers, int32_t param_batch_is_one);
 int64_t jf_gf_chain_inv_bwd_lds_bytes_f32(int32_t D, int32_t n_layers, const jf_gf_layer* layers, int32_t param_batch_is_one);
@@ -162,7 +163,8 @@ int jf_gf_chain_fwd_tab_f64(const double* z, int64_t z_stride, const double* log
  *   param_batch == B: (B, P) rows in the layout of `params` (what the amortisation MLP's backward consumes);
  *   param_batch == 1: jf_gf_chain_inv_bwd_partials(B, D) rows of partial sums (one per workgroup; rows of workgroups that took no tile are zero), to be added up by the caller.  Inside a workgroup the
  *   sums are accumulated in float64 by LDS atomics (both precisions): the float32 result is reproducible in practice, the float64 one to the last
- *   bits only up to the order of those additions.
+ *   bits only up to the order of those additions.  Chains whose accumulators do not fit the LDS (jf_gf_chain_inv_bwd_lds_bytes_* = 0) add
+ *   into the partial rows themselves, by atomics in the precision of g_params.
  * The gradients of log_det_in and base_logp_in are g_log_det and g_base_logp themselves. */
 int64_t jf_gf_chain_inv_bwd_partials(int64_t B, int32_t D);
 int jf_gf_chain_inv_bwd_f32(const float* x, int64_t x_stride, const float* params, int64_t param_stride, int32_t param_batch, int64_t B,

@@ -833,12 +833,14 @@ T_MAX_DIM = 32               # 't' layers: the triangular factor of a row in reg
 LDS_BYTES_PER_CU = 160 * 1024
 
 
-def gf_chain_fits(layer_array, n_layers, D, dtype, bcast, backward=False):
-    """does ONE launch of this chain fit the LDS of a CU (log-prob / sampling direction, or its backward)?"""
+def gf_chain_fits(layer_array, n_layers, D, dtype, bcast, backward=False, on_chip=False):
+    """does ONE launch of this chain fit the LDS of a CU (log-prob / sampling direction, or its backward)?  The broadcast backward of a chain
+    whose accumulators exceed the LDS runs with its accumulators in global memory (the query reports 0 bytes); on_chip=True does not count that
+    slower launch as fitting."""
     suf = "_f32" if dtype == torch.float32 else "_f64"
     fn = getattr(lib(), ("jf_gf_chain_inv_bwd_lds_bytes" if backward else "jf_gf_chain_lds_bytes") + suf)
     n = int(fn(D, n_layers, layer_array, 1 if bcast else 0))
-    return 0 <= n <= LDS_BYTES_PER_CU
+    return (1 if on_chip and backward and bcast else 0) <= n <= LDS_BYTES_PER_CU
 
 
 def cond_gf_chain_inv(inp, w1, b1, w2, b2, x, log_det, layer_array, n_layers, D, x_out=None, base_logp_in=None, want_base_logp=False, status=None):

@@ -30,6 +30,7 @@ namespace jf {
 
 constexpr int GB_MAX_HH = 8;                // reflections kept in registers for groups of up to 8 lanes; wider groups keep G (gb_max_hh)
 template <int G> constexpr int gb_max_hh() { return G > GB_MAX_HH ? G : GB_MAX_HH; }
+constexpr size_t GB_LDS_MAX = 160 * 1024;  // LDS of a CU: broadcast chains whose tables and accumulators need more take gf_chain_bwd_gacc_kernel
 constexpr int GB_NT = 512;                  // threads of a broadcast-regime workgroup: the derived rows / accumulators / records in LDS (~40 KB) are
                                             //   per workgroup, so wider workgroups mean more resident waves per CU (256: 2 per SIMD, 512: 4)
 
@@ -637,6 +638,63 @@ __global__ void __launch_bounds__(BCAST ? GB_NT : 64) gf_chain_bwd_kernel(const 
     }
 }
 
+// GLOBAL-ACCUMULATOR fallback of the broadcast regime: chains whose LDS tables and accumulators above exceed the 160 KB of a CU (one float64
+// layer from D = 47 at num_kde 10, float32 at D = 64 and num_kde 20).  Nothing in LDS: the lanes read the raw parameter row from global memory
+// (the same row for every row of the batch: it stays in the caches), evaluate each layer as the per-sample regime does, and take the log-space
+// backward (gf_layer_bwd, ACC) whose atomics add straight into this workgroup's partial row of g_params.  Only the workgroup's own waves share
+// that row, so the partial rows are summed by the caller in a fixed order as before; inside a row the order of the atomics is not fixed, as
+// for the LDS accumulators.  Roughly 3x the instructions per component of gf_layer_bwd_bcast: off the benchmarked path, it exists so that
+// training works wherever the forward runs.
+template <typename T, int G>
+__global__ void __launch_bounds__(GB_NT) gf_chain_bwd_gacc_kernel(const GfBwdArgs<T> a) {
+    constexpr int NT = GB_NT, R = NT / G;
+    constexpr int LG = G == 1 ? 0 : G == 2 ? 1 : G == 4 ? 2 : G == 8 ? 3 : G == 16 ? 4 : G == 32 ? 5 : 6;
+    const int tid = threadIdx.x;
+    const int g = tid & (G - 1), r = tid >> LG;
+    const int D = a.D, nl = a.n_layers;
+    const bool live = g < D, leader = g == 0;
+    const int d = live ? g : D - 1;
+    T* acc = a.g_params + (int64_t)blockIdx.x * a.gps;
+    for (int j = tid; j < a.n_params_total; j += NT) acc[j] = T(0);
+    if ((int)blockIdx.x >= a.active_blocks) return;               // more partial rows than workgroups with tiles: zero rows
+    __threadfence();                                              // the zeros reach L2, where the atomics below add, before any wave adds
+    __syncthreads();
+    for (int t = 0; t < a.tiles_per_block; ++t) {
+        const int64_t row0 = ((int64_t)blockIdx.x + (int64_t)t * a.active_blocks) * R;
+        if (row0 >= a.B) break;
+        const int64_t row = row0 + r;
+        const bool row_valid = row < a.B;
+        const int64_t rrow = row_valid ? row : a.B - 1;
+        T x = a.x[rrow * a.xs + d];
+        T xreg[JF_MAX_CHAIN];
+#pragma unroll
+        for (int li = 0; li < JF_MAX_CHAIN; ++li) {
+            xreg[li] = x;
+            if (li < nl) {
+                const GfLayerDev<T> o = a.L[nl - 1 - li];
+                const T* p = a.params + o.col0 + d;
+                if (o.model_offset) x -= p[0];
+                x = gfg_rotate_inv<T, G, true>(p, o, D, live, x);
+                x = gf_icdf<T>(o.inv_type, gfg_mixture<T, true>(p, o, D, x)).y;
+            }
+        }
+        const T gl = (a.g_ld && row_valid) ? a.g_ld[rrow] : T(0);
+        T gy = (a.g_xout && row_valid) ? a.g_xout[rrow * a.gxos + d] : T(0);
+        if (a.g_blp && row_valid) gy -= x * a.g_blp[rrow];
+        if (!live || !row_valid) gy = T(0);
+#pragma unroll
+        for (int li = JF_MAX_CHAIN - 1; li >= 0; --li) {
+            if (li < nl) {
+                const GfLayerDev<T> o = a.L[nl - 1 - li];
+                gy = gf_layer_bwd<T, G, true, T>(a.params + o.col0 + d, acc + o.col0 + d, o, D, live && row_valid, xreg[li], gy, gl, 0);
+            }
+        }
+        if (row_valid && live) a.g_x[row * a.gxs + d] = gy;
+        const T bad = group_max<T, G>((live && !M<T>::finite(gy)) ? T(1) : T(0));
+        status_add(a.status, JF_STATUS_NONFINITE, row_valid && leader && bad > T(0));
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------- general-option layers
 // Chains with a layer that uses add_skewness / center_mean / a non-Householder rotation (jf_gf_ext.h) are differentiated in FORWARD mode, like
 // the manifold layers (manifold_bwd_kernels.hip): the very device code of the forward kernel, instantiated on dual numbers, once per input
@@ -811,7 +869,12 @@ static int gb_launch(GfBwdArgs<T> a, bool bcast, hipStream_t st) {
         int n_rec = 0;
         for (int l = 0; l < a.n_layers; ++l) { a.pk0[l] = n_rec; n_rec += a.L[l].K * a.D; }
         const size_t lds = 3 * cell + (acell << slsh) + ((size_t)a.n_layers * (4 * GB_NT + 2 * (G > 8 ? G : 8)) + (size_t)n_rec * 8) * sizeof(T);
-        if (lds > 160 * 1024) return JF_ERR_UNSUPPORTED;
+        if (lds > GB_LDS_MAX) {                                    // the accumulators go to the partial rows in global memory
+            a.active_blocks = (int)(blocks < n_tiles ? blocks : (n_tiles < 1 ? 1 : n_tiles));
+            a.tiles_per_block = (int)((n_tiles + a.active_blocks - 1) / a.active_blocks);
+            jf::launch(gf_chain_bwd_gacc_kernel<T, G>, dim3((unsigned)blocks), dim3(GB_NT), 0, st, a);
+            return check_launch();
+        }
         auto k = gf_chain_bwd_kernel<T, G, true>;
         if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         // one resident round of workgroups takes all tiles (grid stride): each pays the prologue / epilogue once, no tail round
@@ -898,7 +961,8 @@ template <typename T> static int64_t gb_lds_query(int32_t D, int32_t n_layers, c
     const size_t cell = (size_t)n_layers * a.tile_stride * sizeof(T), acell = (size_t)n_layers * a.tile_stride * sizeof(double);
     size_t n_rec = 0;
     for (int l = 0; l < n_layers; ++l) n_rec += (size_t)a.L[l].K * D;
-    return (int64_t)(3 * cell + acell + ((size_t)n_layers * (4 * GB_NT + 2 * (G > 8 ? G : 8)) + n_rec * 8) * sizeof(T));
+    const size_t lds = 3 * cell + acell + ((size_t)n_layers * (4 * GB_NT + 2 * (G > 8 ? G : 8)) + n_rec * 8) * sizeof(T);
+    return lds > GB_LDS_MAX ? 0 : (int64_t)lds;                    // 0: gf_chain_bwd_gacc_kernel, which takes no LDS
 }
 
 }  // namespace jf

@@ -296,7 +296,9 @@ class gf_block(euclidean_base.euclidean_base):
 def chain_fits(layers):
     """does ONE launch of these 'g' layers fit a CU's LDS in every direction the host may ask for (log-prob, sampling, backward; float64,
     broadcast parameters: the most demanding case)?  Wide layers (D > 8: groups of 16 / 32 lanes per row, parameter rows of thousands of
-    values) run as several shorter launches.  Cached per layer list (a ctypes query of the library's own bookkeeping)."""
+    values) run as several shorter launches.  A single layer whose broadcast backward does not fit takes the library's global-accumulator
+    launch; a run of several layers must fit on chip (otherwise it is cut).  Cached per layer list (a ctypes query of the library's own
+    bookkeeping)."""
     key = tuple(id(l) for l in layers)
     cache = layers[0].__dict__.setdefault("_chain_fits_cache", {})
     hit = cache.get(key)
@@ -305,7 +307,7 @@ def chain_fits(layers):
             arr = _hip.gf_layer_array([l.c_struct() for l in layers])
             D = layers[0].dimension
             ext = any(l.has_extended_options for l in layers)
-            hit = all(_hip.gf_chain_fits(arr, len(layers), D, torch.float64, bcast, backward)
+            hit = all(_hip.gf_chain_fits(arr, len(layers), D, torch.float64, bcast, backward, on_chip=len(layers) > 1)
                       for bcast in (True, False) for backward in ((False,) if (ext or any(l.nonlinear_stretch_type != "classic" for l in layers))
                                                                    else (False, True)))
         except _hip.HipUnavailable:

