@@ -8,6 +8,7 @@ layer, MFMA launches for the amortisation MLPs) instead of thousands of eager op
 
 Reference line numbers cited below refer to jammy_flows/main/default.py.
 """
+import contextlib
 import copy
 import os
 
@@ -70,10 +71,7 @@ class HipLinearStack(nn.Sequential):
         if (len(mods) == 3 and isinstance(mods[1], nn.Tanh) and mods[0].in_features <= _hip.MLP2_MAX_IN
                 and mods[0].out_features <= _hip.MLP2_MAX_HIDDEN and mods[0].out_features % 4 == 0):
             # Linear-tanh-Linear (the reference's default "128"): one fused launch, the hidden activations never leave the registers
-            ps = [mods[0].weight, mods[0].bias, mods[2].weight, mods[2].bias]
-            if ps[0].dtype != x.dtype:
-                ps = [p.to(x.dtype) for p in ps]
-            ps = [p.detach() for p in ps]
+            ps = _mlp2_weights(self, x.dtype)
             if (x.dtype == torch.float64 and MLP_MATRIX_ARITHMETIC_F64[0] != "f64" and MLP_I8_MIN_COLS[0] <= ps[2].shape[0] <= (1 << 20)
                     and x.shape[0] >= MLP_I8_MIN_ROWS[0] and mods[0].in_features <= _hip.MLP2_I8_MAX_IN):
                 # wide float64 output (the 548-column parameter block of an e4 block): the float64 matrix cores run at the float64 vector rate, so
@@ -149,20 +147,63 @@ def _layer_groups(layers):
     return groups
 
 
-def _manifold_chain(fam, layers, direction, x, log_det, extra, only_last_first, x_out, base_logp_in, want_base_logp, status, pre_ld=None, pre_blp=None):
-    structs = []
+def _is_mlp2(mlp):
+    """is `mlp` the default amortisation MLP of one hidden layer (HipLinearStack Linear-tanh-Linear), the form the fused block kernels embed?"""
+    return isinstance(mlp, HipLinearStack) and len(mlp) == 3 and isinstance(mlp[1], nn.Tanh)
+
+
+def _mlp2_weights(mlp, dtype):
+    """[w1, b1, w2, b2] of a Linear-tanh-Linear stack in `dtype`, detached"""
+    ps = [mlp[0].weight, mlp[0].bias, mlp[2].weight, mlp[2].bias]
+    if ps[0].dtype != dtype:
+        ps = [p.to(dtype) for p in ps]
+    return [p.detach() for p in ps]
+
+
+def _classic_chain(layers):
+    """are the layers one chain launch of classic 'g' layers of at most 4 dimensions without extended options (the fused block kernels, the
+    merged launch)?"""
+    return (gfl.chain_supported(layers) and layers[0].dimension <= 4
+            and not any(l.nonlinear_stretch_type != "classic" or l.has_extended_options for l in layers))
+
+
+def _default_g_chain(layers):
+    """are the layers 'g' layers of at most 8 dimensions at the default options (10 KDE components, <= 8 reflections, classic stretch, smooth
+    widths, fitted and regulated normalisation) -- what the low-rank chain kernels take?"""
+    if layers[0].dimension > 8:
+        return False
     for l in layers:
-        if fam == "r":
-            structs.append(l.c_struct())
-        else:
-            structs.append(l.c_struct(1 if (only_last_first or l.euclidean_to_sphere_as_first) else 0))
+        c = l.c_struct()
+        if l.has_extended_options:
+            return False
+        if not (c.num_kde == 10 and c.hh_iter <= 8 and c.nonlinear_stretch_type == _hip.GF_STRETCH_CLASSIC and c.width_mode == _hip.GF_WIDTH_SMOOTH
+                and not c.clamp_widths and c.fit_normalization and c.regulate_normalization):
+            return False
+    return True
+
+
+def _tail_params(params, layer):
+    """only_last (:1018): the tail of the block's parameter row that belongs to its last layer `layer` (:1002-1012)"""
+    return params[:, params.shape[1] - layer.total_param_num:]
+
+
+def _mchain_structs(fam, layers, sphere_chart_first=False):
+    """the layers' C structs for a manifold-chain launch.  A sphere layer takes the sphere -> plane chart first when it is the block's first
+    layer, or for every layer with sphere_chart_first (only_last on a sphere: fix_euclidean_to_sphere_first, :1018-1031)"""
+    if fam == "r":
+        return [l.c_struct() for l in layers]
+    return [l.c_struct(1 if (sphere_chart_first or l.euclidean_to_sphere_as_first) else 0) for l in layers]
+
+
+def _manifold_chain(layers, direction, x, log_det, extra, sphere_chart_first, x_out, base_logp_in, want_base_logp, status, pre_ld=None, pre_blp=None):
+    fam = _manifold_family(layers)
     if extra is None:
         rows = [l._params_for(x, None) for l in layers]
         params = torch.cat(rows, dim=1) if len(rows) > 1 else rows[0]
     else:
         params = extra
-    return _hip.mchain(fam, direction, x, log_det, params, structs, layers[0].dimension, x_out=x_out, base_logp_in=base_logp_in,
-                       want_base_logp=want_base_logp, status=status, pre_ld=pre_ld, pre_blp=pre_blp)
+    return _hip.mchain(fam, direction, x, log_det, params, _mchain_structs(fam, layers, sphere_chart_first), layers[0].dimension, x_out=x_out,
+                       base_logp_in=base_logp_in, want_base_logp=want_base_logp, status=status, pre_ld=pre_ld, pre_blp=pre_blp)
 
 
 class pdf(nn.Module):
@@ -224,11 +265,6 @@ class pdf(nn.Module):
         # JF_FUSED_MATRIX_ARITHMETIC=f32 in the environment selects the exact-f32 kernel process-wide (an operational fallback while the
         # full-batch hazard of DESIGN.md 3.9 has a remedy but no root cause).
         self.fused_matrix_arithmetic = os.environ.get("JF_FUSED_MATRIX_ARITHMETIC", "split_f16")
-        # which kernel runs the split-bf16 fused block: "auto" = "split" (cond_split_kernels.hip).  (The persistent ping-pong variant of round 3
-        # measured the same and left the product in round 5: scripts/probe/cond_pp/.)
-        self.fused_block_kernel = os.environ.get("JF_FUSED_BLOCK_KERNEL", "auto")
-        if self.fused_block_kernel not in ("auto", "split"):
-            raise ValueError("JF_FUSED_BLOCK_KERNEL must be 'auto' or 'split', got %r" % self.fused_block_kernel)
         if self.fused_matrix_arithmetic not in ("split_f16", "split_bf16", "f32"):
             raise ValueError("JF_FUSED_MATRIX_ARITHMETIC must be 'split_f16', 'split_bf16' or 'f32', got %r" % self.fused_matrix_arithmetic)
         self._packed_cache = {}
@@ -507,7 +543,7 @@ class pdf(nn.Module):
                     these = these.to(module_device)          # the init vector lands in parameters: keep them on the module's device
                 if len(these) == 0:
                     continue
-                mlp = self.mlp_predictors[si] if len(self.mlp_predictors) > si else None
+                mlp = self._mlp(si)
                 if mlp is not None and self.predict_log_normalization and self.join_poisson_and_pdf_description and si == 0:
                     these = torch.cat([these, torch.tensor([0.1], dtype=these.dtype, device=these.device)])      # log-lambda at initialisation (:1893-1896)
                 if mlp is not None:
@@ -629,37 +665,35 @@ class pdf(nn.Module):
             return torch.cat(embeds, dim=1) if len(embeds) > 1 else embeds[0]
         raise Exception("extra conditional input is empty but required for encoding!")
 
-    def _fusable_block(self, si, layers, only_last, amort, dtype):
-        """can sub-pdf si run as ONE fused launch (amortisation MLP + its g layers, parameter block kept on chip)?"""
+    def _mlp(self, si):
+        """the amortisation MLP of sub-pdf si, or None"""
+        return self.mlp_predictors[si] if len(self.mlp_predictors) > si else None
+
+    def _fusion_mlp(self, si, only_last, amort):
+        """the gate every one-launch block (amortisation MLP + flow in ONE kernel) passes: the MLP of sub-pdf si, or None when its output is not
+        the block's whole parameter row or fusing is off"""
         if self._poisson_column(si):                       # the MLP emits one more column than the block has parameters
             return None
         if not self.fuse_conditional_blocks or only_last or amort is not None or _hip.BINS_LOG is not None:
             return None
+        return self._mlp(si)
+
+    def _fusable_block(self, si, layers, only_last, amort, dtype):
+        """can sub-pdf si run as ONE fused launch (amortisation MLP + its g layers, parameter block kept on chip)?"""
+        mlp = self._fusion_mlp(si, only_last, amort)
         if dtype != torch.float32:      # measured: in float64 the two-launch path (jf_mlp2 + jf_gf_chain_inv) is faster
             return None
-        mlp = self.mlp_predictors[si] if len(self.mlp_predictors) > si else None
-        if not isinstance(mlp, HipLinearStack) or len(mlp) != 3 or not isinstance(mlp[1], nn.Tanh):
-            return None
-        if not (3 <= layers[0].dimension <= 4) or not gfl.chain_supported(layers):
-            return None
-        if any(l.nonlinear_stretch_type != "classic" or l.has_extended_options for l in layers):
+        if not _is_mlp2(mlp) or layers[0].dimension < 3 or not _classic_chain(layers):
             return None
         if mlp[0].in_features > _hip.COND_GF_MAX_IN or mlp[0].out_features > _hip.COND_GF_MAX_HIDDEN or mlp[0].out_features % 4:
             return None
-        ps = [mlp[0].weight, mlp[0].bias, mlp[2].weight, mlp[2].bias]
-        if ps[0].dtype != dtype:
-            ps = [p.to(dtype) for p in ps]
-        return [p.detach() for p in ps]
+        return _mlp2_weights(mlp, dtype)
 
     def _fusable_manifold_block(self, si, layers, only_last, amort, dtype):
         """sub-pdf si = default amortisation MLP (Linear-tanh-Linear) + one chain of 'r' / 'o' / 'm' / 'f' layers with <= 64 parameters per
         row: (family, [w1, b1, w2, b2]) for jf_cond_<fam>_chain_inv, else None"""
-        if self._poisson_column(si):                       # the MLP emits one more column than the block has parameters
-            return None
-        if not self.fuse_conditional_blocks or only_last or amort is not None or _hip.BINS_LOG is not None:
-            return None
-        mlp = self.mlp_predictors[si] if len(self.mlp_predictors) > si else None
-        if not isinstance(mlp, HipLinearStack) or len(mlp) != 3 or not isinstance(mlp[1], nn.Tanh):
+        mlp = self._fusion_mlp(si, only_last, amort)
+        if not _is_mlp2(mlp):
             return None
         fam = _manifold_family(layers)
         if fam is None or fam not in _hip.COND_MCHAIN_FAMILIES:
@@ -674,34 +708,33 @@ class pdf(nn.Module):
             return None
         if fam == "f" and any(getattr(l, "add_correlated_rq_spline_flow", 0) for l in layers):
             return None
-        ps = [mlp[0].weight, mlp[0].bias, mlp[2].weight, mlp[2].bias]
-        if ps[0].dtype != dtype:
-            ps = [p.to(dtype) for p in ps]
-        return fam, [p.detach() for p in ps]
+        return fam, _mlp2_weights(mlp, dtype)
 
     def _fusable_lowrank_block(self, si, layers, only_last, amort, like):
         """sub-pdf si = a two-stage AmortizableMLP with a low-rank last stage + chainable g layers at default options: the weight views for
         jf_amlp_gf_chain_inv (v1, u1, b1, v2, u2, b2), else None"""
-        if self._poisson_column(si):                       # the MLP emits one more column than the block has parameters
-            return None
-        if not self.fuse_conditional_blocks or only_last or amort is not None or _hip.BINS_LOG is not None:
-            return None
-        mlp = self.mlp_predictors[si] if len(self.mlp_predictors) > si else None
+        mlp = self._fusion_mlp(si, only_last, amort)
         if not isinstance(mlp, AmortizableMLP) or mlp.highway_mode != 0 or not mlp.use_permanent_parameters or len(mlp.stages or []) != 2:
             return None
         s1, s2 = mlp.stages
         if s2["full"] or s2["rank"] > 16 or (not s1["full"] and s1["rank"] > 16) or s1["inp"] > 32 or s1["out"] > 128:
             return None
-        if not gfl.chain_supported(layers) or layers[0].dimension > 8:
+        if not gfl.chain_supported(layers) or not _default_g_chain(layers):
             return None
-        for l in layers:
-            c = l.c_struct()
-            if l.has_extended_options:
-                return None
-            if not (c.num_kde == 10 and c.hh_iter <= 8 and c.nonlinear_stretch_type == _hip.GF_STRETCH_CLASSIC and c.width_mode == _hip.GF_WIDTH_SMOOTH
-                    and not c.clamp_widths and c.fit_normalization and c.regulate_normalization):
-                return None
         return mlp.lowrank_views(mlp._flat(like))
+
+    def _fused_route(self, si, layers, kind, only_last, amort, x):
+        """the one-launch route of sub-pdf si in the log-prob and sampling loops: ("g", [w1, b1, w2, b2]) -- Linear-tanh-Linear MLP + g layers,
+        jf_cond_gf_chain_*; ("lowrank", weight views) -- low-rank AmortizableMLP + g layers, jf_amlp_gf_chain_*; ("m", (family, [w1, b1, w2,
+        b2])) -- Linear-tanh-Linear MLP + a manifold chain, jf_cond_<fam>_chain_*; else (None, None): the parameter row, then the flow"""
+        if kind != "e":
+            mf = self._fusable_manifold_block(si, layers, only_last, amort, x.dtype)
+            return ("m", mf) if mf is not None else (None, None)
+        fused = self._fusable_block(si, layers, only_last, amort, x.dtype)
+        if fused is not None:
+            return "g", fused
+        lowrank = self._fusable_lowrank_block(si, layers, only_last, amort, x)
+        return ("lowrank", lowrank) if lowrank is not None else (None, None)
 
     def _lowrank_chain_ok(self, si, layers, only_last, amort, x, mlp):
         """gradient mode: sub-pdf si can run autograd.LowRankGfChainFn (float64, last MLP stage low-rank with rank <= 8, <= 8 dimensions,
@@ -713,16 +746,7 @@ class pdf(nn.Module):
         last = mlp.stages[-1]
         if last["full"] or last["num_b"] == 0 or last["act"] or last["rank"] > _hip.LOWRANK_GF_MAX_RANK or len(mlp.sub_mlps) != 1:
             return False
-        if layers[0].dimension > 8 or x.shape[0] == 0:
-            return False
-        for l in layers:
-            c = l.c_struct()
-            if l.has_extended_options:
-                return False
-            if not (c.num_kde == 10 and c.hh_iter <= 8 and c.nonlinear_stretch_type == _hip.GF_STRETCH_CLASSIC and c.width_mode == _hip.GF_WIDTH_SMOOTH
-                    and not c.clamp_widths and c.fit_normalization and c.regulate_normalization):
-                return False
-        return True
+        return x.shape[0] > 0 and _default_g_chain(layers)
 
     def _merge_candidate(self, x, data_summary, only_last, amort):
         """do the first two blocks of this log-prob step share a launch (csrc/merged_kernels.hip)?  They must be an unconditional broadcast g
@@ -738,14 +762,11 @@ class pdf(nn.Module):
             kinds = []
             for si in (0, 1):
                 layers = list(self.layer_list[si])
-                kind = self.pdf_defs_list[si][0]
-                mlp = self.mlp_predictors[si] if len(self.mlp_predictors) > si else None
                 k = None
-                if kind == "e" and mlp is None and not self.amortize_everything:
-                    if (gfl.chain_supported(layers) and layers[0].dimension <= 4
-                            and not any(l.nonlinear_stretch_type != "classic" or l.has_extended_options for l in layers)):
+                if self.pdf_defs_list[si][0] == "e":
+                    if self._mlp(si) is None and not self.amortize_everything and _classic_chain(layers):
                         k = 0
-                elif kind != "e" and len(layers) == 1:
+                elif len(layers) == 1:
                     mf = self._fusable_manifold_block(si, layers, False, None, x.dtype)
                     if mf is not None and mf[0] == "f":
                         k = 1
@@ -754,19 +775,13 @@ class pdf(nn.Module):
             self._merge_ok[key] = hit
         return hit
 
-    def _fused_kernel_kind(self, n_rows):
-        """which arithmetic of the register-resident fused block kernel (cond_split_kernels.hip): "split16" (f16 pairs, the default) or
-        "split" (bf16 triples)"""
-        if self.fused_matrix_arithmetic == "split_f16":
-            return "split16"
-        return "split"
-
-    def _packed_w2(self, si, w2, b2, layer_array, n_layers, D, n_rows, kind=None):
-        """(kind, packed split-bf16 image) of the block's output layer for the fused kernel chosen for this batch size, or None when the layer
-        options are outside the kernels' set.  Rebuilt when the weights change: the key is the identity and in-place version of the MODULE's
-        parameters (w2 / b2 may be casts of them made for this call -- fresh temporaries whose own version is always 0 and whose addresses
-        the caching allocator hands out again), plus dtype, device and kernel kind."""
-        kind = kind or self._fused_kernel_kind(n_rows)
+    def _packed_w2(self, si, w2, b2, layer_array, n_layers, D):
+        """(kind, packed image) of the block's output layer for the register-resident fused block kernel (cond_split_kernels.hip) -- kind
+        "split16" (f16 pairs, the default) or "split" (bf16 triples), by fused_matrix_arithmetic -- or None when the layer options are outside
+        the kernels' set.  Rebuilt when the weights change: the key is the identity and in-place version of the MODULE's parameters (w2 / b2
+        may be casts of them made for this call -- fresh temporaries whose own version is always 0 and whose addresses the caching allocator
+        hands out again), plus dtype, device and kernel kind."""
+        kind = "split16" if self.fused_matrix_arithmetic == "split_f16" else "split"
         lin = self.mlp_predictors[si][2]
         key = (id(lin.weight), lin.weight._version, lin.weight.data_ptr(), id(lin.bias), lin.bias._version, lin.bias.data_ptr(), str(w2.dtype),
                str(w2.device), kind)
@@ -782,7 +797,7 @@ class pdf(nn.Module):
 
     def _block_params(self, si, data_summary, embeds, amort, counter):
         """extra_inputs row block of sub-pdf si, or None for permanent parameters (:936-993, 1420-1475)."""
-        mlp = self.mlp_predictors[si] if len(self.mlp_predictors) > si else None
+        mlp = self._mlp(si)
         if mlp is not None:
             inp = self._mlp_input(si, data_summary, embeds)
             if not isinstance(mlp, HipLinearStack):
@@ -915,178 +930,120 @@ class pdf(nn.Module):
         if lanes:
             rec.fork()
         n_blocks = len(self.layer_list)
+        # the last block may add the earlier blocks' sums in its epilogue (list order, itself last: the bits of combine_rows) and write
+        # log_prob = log_prob_base + log_det itself (:1110-1117): one launch fewer per step
+        fold_last = independent and want_base_logp and not lanes and not overlap and self.fold_combine
         folded_total = None
         if merge:
             _hip.merge_begin()
         try:
-            return self._inverse_blocks(x, log_det, data_summary, amortization_parameters, force_embedding_coordinates, force_intrinsic_coordinates,
-                                        only_last, want_base_logp, status, per_block, B, base, base_logp, embeds, lazy, counter, independent,
-                                        ld_parts, blp_parts, rec, lanes, overlap, n_blocks, folded_total, merge)
+            for si, block in enumerate(self.layer_list):      # (:998-1031)
+                if merge and si == 2:
+                    _hip.merge_end(x)                     # the first two blocks go out as one launch; the rest follows launch by launch
+                if independent:
+                    if si > 0:
+                        ld_parts.append(log_det)
+                        if want_base_logp:
+                            blp_parts.append(base_logp)
+                    log_det, base_logp = None, None
+                    if lanes:                             # the last block stays on the caller's stream
+                        rec.set_lane(0 if si == n_blocks - 1 else 1 + si % (self.plan_lanes - 1))
+                    if overlap and si == 1:               # the blocks after the first may run beside their predecessors (no barrier bit)
+                        rec.set_any_order(True)
+                a, b = self.target_dim_indices[si]
+                tgt = x[:, a:b]
+                ba, bb = self.base_dim_indices[si]
+                out_view = base[:, ba:bb]
+                layers = list(block)
+                kind = self.pdf_defs_list[si][0]
+                D = layers[0].dimension
+                fold_here = fold_last and si == n_blocks - 1
+                route, w = self._fused_route(si, layers, kind, only_last, amortization_parameters, x)
+                res, fold = None, False                   # fold: this launch added the step's sums up itself, res[3] = log_prob
+                if route == "g":
+                    # amortisation MLP + g layers in one launch: the per-sample parameter block never reaches HBM
+                    larr = _hip.gf_layer_array([l.c_struct() for l in layers])
+                    packed = None
+                    if self.fused_matrix_arithmetic != "f32" and w[0].shape[0] <= 128:
+                        packed = self._packed_w2(si, w[2], w[3], larr, len(layers), D)
+                    if packed is not None:
+                        mlp_in = self._mlp_input(si, data_summary, embeds)
+                        if fold_here:
+                            res = _hip.cond_gf_chain_inv_split(mlp_in, w[0], w[1], packed[1], tgt, None, larr, len(layers), D, x_out=out_view,
+                                                               want_base_logp=True, status=status, kind=packed[0],
+                                                               pre_ld=[t for t in ld_parts if t is not None], pre_blp=[t for t in blp_parts if t is not None])
+                            fold = res is not None
+                        if res is None:
+                            res = _hip.cond_gf_chain_inv_split(mlp_in, w[0], w[1], packed[1], tgt, log_det, larr, len(layers), D, x_out=out_view,
+                                                               base_logp_in=base_logp, want_base_logp=want_base_logp, status=status, kind=packed[0])
+                    else:
+                        res = _hip.cond_gf_chain_inv(_hip.as_matrix(self._mlp_input(si, data_summary, embeds)), *w, tgt, log_det, larr, len(layers), D,
+                                                     x_out=out_view, base_logp_in=base_logp, want_base_logp=want_base_logp, status=status)
+                elif route == "lowrank":
+                    # low-rank AmortizableMLP + g layers in one launch: the parameter block is regenerated per lane from the row's rank-space vector
+                    res = _hip.amlp_gf_chain_inv(_hip.as_matrix(self._mlp_input(si, data_summary, embeds)), *w, tgt, log_det,
+                                                 _hip.gf_layer_array([l.c_struct() for l in layers]), len(layers), D,
+                                                 x_out=out_view, base_logp_in=base_logp, want_base_logp=want_base_logp, status=status)
+                elif route == "m":
+                    # default amortisation MLP + the manifold chain in one launch: the parameter rows stay in LDS (None: declined)
+                    fam, ws = w
+                    res = _hip.cond_mchain_inv(fam, _hip.as_matrix(self._mlp_input(si, data_summary, embeds)), *ws, tgt, log_det,
+                                               _mchain_structs(fam, layers), D, x_out=out_view, base_logp_in=base_logp, want_base_logp=want_base_logp,
+                                               status=status)
+                if res is None:
+                    extra, counter = self._block_params(si, data_summary, embeds, amortization_parameters, counter)
+                    if only_last:
+                        layers = layers[-1:]
+                        extra = None if extra is None else _tail_params(extra, layers[0])
+                    if kind == "e" and gfl.chain_supported(layers):
+                        # a pdf that is (or, threading the sums, ends with) one plain g chain: the chain launch writes log_prob = base + log_det itself
+                        fold = (want_base_logp and not independent and si == n_blocks - 1 and per_block is None and self.fold_combine
+                                and not force_embedding_coordinates and not force_intrinsic_coordinates)
+                        res = gfl.run_chain(layers, "inv", tgt, log_det, gfl.chain_permanent_row(layers, x) if extra is None else extra, x_out=out_view,
+                                            base_logp_in=base_logp, want_base_logp=want_base_logp, status=status, want_total=fold)
+                    elif _manifold_family(layers) is not None:
+                        pl = pb_ = None
+                        if fold_here and _hip.BINS_LOG is None:
+                            # the last block adds the earlier blocks' sums itself and writes log_prob (as the fused g block does): no combine launch
+                            pl, pb_ = [t for t in ld_parts if t is not None], [t for t in blp_parts if t is not None]
+                            if len(pl) > _hip.COND_GF_MAX_PRE or len(pb_) > _hip.COND_GF_MAX_PRE:
+                                pl = pb_ = None
+                        fold = pl is not None
+                        res = _manifold_chain(layers, "inv", tgt, log_det, extra, only_last and kind == "s", out_view, base_logp, want_base_logp, status,
+                                              pre_ld=pl, pre_blp=pb_)
+                    else:
+                        if log_det is None:
+                            log_det = torch.zeros(B, dtype=x.dtype, device=x.device)
+                        cur, end = tgt, 0 if extra is None else extra.shape[1]
+                        for grp in reversed(_layer_groups(layers)):       # tail-first parameter slices (:1002-1012)
+                            n = sum(l.total_param_num for l in grp)
+                            this = None if extra is None else extra[:, end - n:end]
+                            if type(grp[0]) is gfl.gf_block and not only_last:
+                                cur, log_det = gfl.run_chain(grp, "inv", cur, log_det, this if this is not None else gfl.chain_permanent_row(grp, x),
+                                                             status=status)[:2]
+                            else:
+                                kw = {"fix_euclidean_to_sphere_first": True} if (only_last and kind == "s") else {}
+                                cur, log_det = grp[0].inv_flow_mapping([cur, log_det], extra_inputs=this, **kw)[:2]
+                            end -= n
+                        out_view.copy_(cur)
+                        if want_base_logp:
+                            base_logp = _hip.normal_logp(out_view, base_logp)
+                        res = (out_view, log_det, base_logp)
+                log_det = res[1]
+                if want_base_logp:
+                    base_logp = res[2]
+                if fold:
+                    folded_total = res[3]
+                if lazy:
+                    embeds.append(block[-1]._embedding_conditional_return(tgt))
+                if per_block is not None:
+                    per_block.append(log_det)
+            if merge and n_blocks == 2:
+                _hip.merge_end(x)                         # (a pdf of two blocks: both were captured)
         except BaseException:
             if merge:
                 _hip.merge_abort()
             raise
-
-    def _inverse_blocks(self, x, log_det, data_summary, amortization_parameters, force_embedding_coordinates, force_intrinsic_coordinates,
-                        only_last, want_base_logp, status, per_block, B, base, base_logp, embeds, lazy, counter, independent, ld_parts, blp_parts,
-                        rec, lanes, overlap, n_blocks, folded_total, merge):
-        """the block loop of _inverse_impl (:998-1031)"""
-        for si, block in enumerate(self.layer_list):
-            if merge and si == 2:
-                _hip.merge_end(x)                         # the first two blocks go out as one launch; the rest follows launch by launch
-                merge = False
-            if independent:
-                if si > 0:
-                    ld_parts.append(log_det)
-                    if want_base_logp:
-                        blp_parts.append(base_logp)
-                log_det, base_logp = None, None
-                if lanes:                                 # the last block stays on the caller's stream
-                    rec.set_lane(0 if si == n_blocks - 1 else 1 + si % (self.plan_lanes - 1))
-                if overlap and si == 1:                   # the blocks after the first may run beside their predecessors (no barrier bit)
-                    rec.set_any_order(True)
-            a, b = self.target_dim_indices[si]
-            tgt = x[:, a:b]
-            ba, bb = self.base_dim_indices[si]
-            out_view = base[:, ba:bb]
-            layers = list(block)
-            kind = self.pdf_defs_list[si][0]
-            fused = self._fusable_block(si, layers, only_last, amortization_parameters, x.dtype) if kind == "e" else None
-            if fused is not None:
-                # amortisation MLP + g layers in one launch: the per-sample parameter block never reaches HBM
-                larr = _hip.gf_layer_array([l.c_struct() for l in layers])
-                packed = None
-                if self.fused_matrix_arithmetic != "f32" and fused[0].shape[0] <= 128:
-                    packed = self._packed_w2(si, fused[2], fused[3], larr, len(layers), layers[0].dimension, x.shape[0])
-                if packed is not None:
-                    mlp_in = self._mlp_input(si, data_summary, embeds)
-                    res = None
-                    if independent and want_base_logp and si == n_blocks - 1 and not lanes and not overlap and self.fold_combine:
-                        # the last block adds the earlier blocks' sums in its epilogue (list order, itself last: the bits of combine_rows) and
-                        # writes log_prob = log_prob_base + log_det itself (:1110-1117): one launch fewer per step
-                        res = _hip.cond_gf_chain_inv_split(mlp_in, fused[0], fused[1], packed[1], tgt, None, larr, len(layers), layers[0].dimension,
-                                                           x_out=out_view, want_base_logp=True, status=status, kind=packed[0],
-                                                           pre_ld=[t for t in ld_parts if t is not None], pre_blp=[t for t in blp_parts if t is not None])
-                        if res is not None:
-                            folded_total = res[3]
-                    if res is None:
-                        res = _hip.cond_gf_chain_inv_split(mlp_in, fused[0], fused[1], packed[1], tgt, log_det, larr,
-                                                           len(layers), layers[0].dimension, x_out=out_view, base_logp_in=base_logp,
-                                                           want_base_logp=want_base_logp, status=status, kind=packed[0])
-                else:
-                    res = _hip.cond_gf_chain_inv(_hip.as_matrix(self._mlp_input(si, data_summary, embeds)), *fused, tgt, log_det, larr, len(layers),
-                                                 layers[0].dimension, x_out=out_view, base_logp_in=base_logp, want_base_logp=want_base_logp,
-                                                 status=status)
-                log_det = res[1]
-                if want_base_logp:
-                    base_logp = res[2]
-                if lazy:
-                    embeds.append(block[-1]._embedding_conditional_return(tgt))
-                if per_block is not None:
-                    per_block.append(log_det)
-                continue
-            lowrank = self._fusable_lowrank_block(si, layers, only_last, amortization_parameters, x) if kind == "e" else None
-            if lowrank is not None:
-                # low-rank AmortizableMLP + g layers in one launch: the parameter block is regenerated per lane from the row's rank-space vector
-                res = _hip.amlp_gf_chain_inv(_hip.as_matrix(self._mlp_input(si, data_summary, embeds)), *lowrank, tgt, log_det,
-                                             _hip.gf_layer_array([l.c_struct() for l in layers]), len(layers), layers[0].dimension,
-                                             x_out=out_view, base_logp_in=base_logp, want_base_logp=want_base_logp, status=status)
-                log_det = res[1]
-                if want_base_logp:
-                    base_logp = res[2]
-                if lazy:
-                    embeds.append(block[-1]._embedding_conditional_return(tgt))
-                if per_block is not None:
-                    per_block.append(log_det)
-                continue
-            mfused = self._fusable_manifold_block(si, layers, only_last, amortization_parameters, x.dtype) if kind != "e" else None
-            if mfused is not None:
-                # default amortisation MLP + the manifold chain in one launch: the parameter rows stay in LDS
-                fam, ws = mfused
-                structs = [l.c_struct() if fam == "r" else l.c_struct(1 if l.euclidean_to_sphere_as_first else 0) for l in layers]
-                res = _hip.cond_mchain_inv(fam, _hip.as_matrix(self._mlp_input(si, data_summary, embeds)), *ws, tgt, log_det, structs, layers[0].dimension,
-                                           x_out=out_view, base_logp_in=base_logp, want_base_logp=want_base_logp, status=status)
-                if res is not None:
-                    log_det = res[1]
-                    if want_base_logp:
-                        base_logp = res[2]
-                    if lazy:
-                        embeds.append(block[-1]._embedding_conditional_return(tgt))
-                    if per_block is not None:
-                        per_block.append(log_det)
-                    continue
-            extra, counter = self._block_params(si, data_summary, embeds, amortization_parameters, counter)
-            if only_last:
-                layers = layers[-1:]
-            if kind == "e" and gfl.chain_supported(layers):
-                if extra is None:
-                    params = gfl.chain_permanent_row(layers, x)
-                elif only_last:
-                    params = extra[:, extra.shape[1] - layers[0].total_param_num:]
-                else:
-                    params = extra
-                # a pdf that is (or, threading the sums, ends with) one plain g chain: the chain launch writes log_prob = base + log_det itself
-                tot = (want_base_logp and not independent and si == n_blocks - 1 and per_block is None and self.fold_combine
-                       and not force_embedding_coordinates and not force_intrinsic_coordinates)
-                res = gfl.run_chain(layers, "inv", tgt, log_det, params, x_out=out_view, base_logp_in=base_logp,
-                                    want_base_logp=want_base_logp, status=status, want_total=tot)
-                log_det = res[1]
-                if want_base_logp:
-                    base_logp = res[2]
-                if tot:
-                    folded_total = res[3]
-            elif _manifold_family(layers) is not None:
-                params = extra
-                if extra is not None and only_last:
-                    params = extra[:, extra.shape[1] - layers[0].total_param_num:]
-                pl = pb_ = None
-                if (independent and want_base_logp and si == n_blocks - 1 and not lanes and not overlap and self.fold_combine
-                        and _hip.BINS_LOG is None):
-                    # the last block adds the earlier blocks' sums itself and writes log_prob (as the fused g block does): no combine launch
-                    pl, pb_ = [t for t in ld_parts if t is not None], [t for t in blp_parts if t is not None]
-                    if len(pl) > _hip.COND_GF_MAX_PRE or len(pb_) > _hip.COND_GF_MAX_PRE:
-                        pl = pb_ = None
-                res = _manifold_chain(_manifold_family(layers), layers, "inv", tgt, log_det, params, only_last and kind == "s", out_view,
-                                      base_logp, want_base_logp, status, pre_ld=pl, pre_blp=pb_)
-                log_det = res[1]
-                if want_base_logp:
-                    base_logp = res[2]
-                if pl is not None:
-                    folded_total = res[3]
-            else:
-                if log_det is None:
-                    log_det = torch.zeros(B, dtype=x.dtype, device=x.device)
-                cur = tgt
-                used = 0
-                for grp in reversed(_layer_groups(list(block))):       # tail-first parameter slices (:1002-1012)
-                    n = sum(l.total_param_num for l in grp)
-                    this = None
-                    if extra is not None:
-                        end = extra.shape[1] - used
-                        this = extra[:, end - n:end]
-                    if type(grp[0]) is gfl.gf_block and not only_last:
-                        cur, log_det = gfl.run_chain(grp, "inv", cur, log_det, this if this is not None else gfl.chain_permanent_row(grp, x),
-                                                     status=status)[:2]
-                    else:
-                        l = grp[-1]
-                        if this is not None and len(grp) > 1:
-                            this = this[:, n - l.total_param_num:]
-                        kw = {}
-                        if only_last and kind == "s":
-                            kw["fix_euclidean_to_sphere_first"] = True
-                        cur, log_det = l.inv_flow_mapping([cur, log_det], extra_inputs=this, **kw)[:2]
-                    used += n
-                    if only_last:
-                        break
-                out_view.copy_(cur)
-                if want_base_logp:
-                    base_logp = _hip.normal_logp(out_view, base_logp)
-            if lazy:
-                embeds.append(block[-1]._embedding_conditional_return(tgt))
-            if per_block is not None:
-                per_block.append(log_det)
-        if merge:
-            _hip.merge_end(x)                             # (a pdf of two blocks: both were captured)
         total = None
         if folded_total is not None:
             total = folded_total                          # log_det / base_logp are the totals already
@@ -1165,7 +1122,7 @@ class pdf(nn.Module):
                                                        conditional_input.data_ptr() % 16),
                bool(force_embedding_coordinates), bool(force_intrinsic_coordinates),
                # the switches that choose kernels: a plan replays the choice made when it was recorded
-               self.fuse_conditional_blocks, self.fused_matrix_arithmetic, self.fused_block_kernel, self.force_fused_manifold_blocks,
+               self.fuse_conditional_blocks, self.fused_matrix_arithmetic, self.force_fused_manifold_blocks,
                self.plan_lanes, self.plan_overlap_blocks, self.fold_combine, self.merge_max_rows)
         plan = self._step_plans.get(key)
         if plan is None:
@@ -1234,15 +1191,9 @@ class pdf(nn.Module):
             assert amort.shape[1] == self.total_number_amortizable_params
         counter = 0
 
-        def last_only(layers, params, kind):
-            """only_last (:1018): the block's last layer alone, with the tail of the block's parameter row (:1002-1012)"""
-            if kind not in ("e", "s", "i"):
-                raise Exception("Flow type ", kind, " does not supported *only_last*!")
-            return layers[-1:], params[:, params.shape[1] - layers[-1].total_param_num:]
-
-        def block_params(si, layers, inp, mlp):
-            """(parameter block with grad, new counter): MLP output (own or per-sample weights), a slice of the amortisation block, or the
-            permanent parameters (:936-993)"""
+        def block_params(si, kind, layers, inp, mlp):
+            """(layers to run, their parameter block with grad): the MLP output (own or per-sample weights), a slice of the amortisation block,
+            or the permanent parameters (:936-993); only_last (:1018): the block's last layer alone, with the tail of the row"""
             nonlocal counter
             if mlp is not None:
                 if amort is not None:
@@ -1251,13 +1202,18 @@ class pdf(nn.Module):
                     counter += n
                 else:
                     out = mlp(inp)
-                return out[:, :-1] if self._poisson_column(si) else out
-            if self.amortize_everything:
+                out = out[:, :-1] if self._poisson_column(si) else out
+            elif self.amortize_everything:
                 n = sum(l.get_total_param_num() for l in layers)
                 out = amort[:, counter:counter + n]
                 counter += n
-                return out
-            return self._permanent_row_with_grad(layers, x)
+            else:
+                out = self._permanent_row_with_grad(layers, x)
+            if not only_last:
+                return layers, out
+            if kind not in ("e", "s", "i"):
+                raise Exception("Flow type ", kind, " does not supported *only_last*!")
+            return layers[-1:], _tail_params(out, layers[-1])
         _hip.require_device(x)
         self._poll_status()
         _hip.release_keepalive()                 # (tensors of the previous step that crossed streams: the streams have met since, _hip.KEEPALIVE)
@@ -1283,7 +1239,7 @@ class pdf(nn.Module):
             tgt = x[:, a:b]
             layers = list(block)
             kind = self.pdf_defs_list[si][0]
-            mlp = self.mlp_predictors[si] if len(self.mlp_predictors) > si else None
+            mlp = self._mlp(si)
             inp = None
             if mlp is not None:
                 pieces = []
@@ -1293,7 +1249,7 @@ class pdf(nn.Module):
                 if not pieces:
                     raise Exception("extra conditional input is empty but required for encoding!")
                 inp = torch.cat(pieces, dim=1) if len(pieces) > 1 else pieces[0]
-            stream_ctx = None
+            st = None
             if side is not None:
                 log_det, base_logp = None, None
                 if si < n_blocks - 1:                     # the last (usually largest) block stays on the caller's stream
@@ -1304,9 +1260,7 @@ class pdf(nn.Module):
                     _hip.keep_alive(x, inp, amort, *embeds)
                     if conditional_input is not None:
                         _hip.keep_alive(*(conditional_input if type(conditional_input) == list else [conditional_input]))
-                    stream_ctx = torch.cuda.stream(st)
-                    stream_ctx.__enter__()
-            try:
+            with torch.cuda.stream(st) if st is not None else contextlib.nullcontext():
                 if kind == "e" and gfl.chain_supported(layers):
                     D = layers[0].dimension
                     fused = self._fusable_block(si, layers, only_last, amort, x.dtype) if mlp is not None else None
@@ -1315,7 +1269,7 @@ class pdf(nn.Module):
                         w1, b1, w2, b2 = mlp[0].weight, mlp[0].bias, mlp[2].weight, mlp[2].bias
                         packed = None
                         if self.fused_matrix_arithmetic != "f32" and w1.shape[0] <= 128:
-                            packed = self._packed_w2(si, w2.detach(), b2.detach(), larr, len(layers), D, x.shape[0])
+                            packed = self._packed_w2(si, w2.detach(), b2.detach(), larr, len(layers), D)
                         out, log_det, base_logp = autograd.CondBlockFn.apply(inp, w1, b1, w2, b2, tgt, log_det, base_logp, packed, larr, len(layers), D,
                                                                              status)
                     elif self._lowrank_chain_ok(si, layers, only_last, amort, x, mlp):
@@ -1324,27 +1278,32 @@ class pdf(nn.Module):
                         larr = _hip.gf_layer_array([l.c_struct() for l in layers])
                         out, log_det, base_logp = autograd.LowRankGfChainFn.apply(t2, u2, b2, tgt, log_det, base_logp, larr, len(layers), D, status)
                     else:
-                        params = block_params(si, layers, inp, mlp)
-                        used = layers
-                        if only_last:
-                            used, params = last_only(layers, params, kind)
+                        used, params = block_params(si, kind, layers, inp, mlp)
                         larr = _hip.gf_layer_array([l.c_struct() for l in used])
                         out, log_det, base_logp = autograd.GfChainInvFn.apply(tgt, log_det, params, base_logp, larr, len(used), D, status)
-                elif kind == "e":
-                    # Euclidean block mixing 'g' runs with other layers ('t'): one launch per group, last group first (:1002-1012)
+                else:
+                    # a block of several launches, last group first, parameters sliced tail-first (:1002-1012): a Euclidean block mixing 'g' runs
+                    # with other layers ('t'), or a manifold block (mixed families, e.g. "mo": one launch per layer)
                     from ..layers.euclidean.multivariate_normal import mvn_block
-                    params = block_params(si, layers, inp, mlp)
-                    used = layers
-                    if only_last:
-                        used, params = last_only(layers, params, kind)
-                    groups = _layer_groups(used)
+                    used, params = block_params(si, kind, layers, inp, mlp)
+                    if kind == "e":
+                        groups = _layer_groups(used)
+                    else:
+                        groups = [used] if _manifold_family(used) is not None else [[l] for l in used]
                     out, c1 = tgt, params.shape[1]
                     for gi in range(len(groups) - 1, -1, -1):
                         grp = groups[gi]
+                        fam = _manifold_family(grp) if kind != "e" else None
+                        if kind != "e" and fam is None:
+                            raise NotImplementedError("gradients through %s layers are not implemented" % type(grp[0]).__name__)
                         n = sum(l.total_param_num for l in grp)
                         this = params[:, c1 - n:c1]
                         blp_in = base_logp if gi == 0 else None
-                        if type(grp[0]) is gfl.gf_block:
+                        if fam is not None:
+                            # (only_last on a sphere: the last layer also takes the sphere -> plane chart, fix_euclidean_to_sphere_first, :1018-1031)
+                            out, log_det, blp = autograd.MChainInvFn.apply(out, log_det, this, blp_in, fam,
+                                                                           _mchain_structs(fam, grp, only_last and kind == "s"), grp[0].dimension, status)
+                        elif type(grp[0]) is gfl.gf_block:
                             larr = _hip.gf_layer_array([l.c_struct() for l in grp])
                             out, log_det, blp = autograd.GfChainInvFn.apply(out, log_det, this, blp_in, larr, len(grp), grp[0].dimension, status)
                         elif type(grp[0]) is mvn_block:
@@ -1364,31 +1323,7 @@ class pdf(nn.Module):
                                     blp = blp_in + blp
                         c1 -= n
                     base_logp = blp
-                else:
-                    params = block_params(si, layers, inp, mlp)
-                    used = layers
-                    if only_last:
-                        used, params = last_only(layers, params, kind)
-                    fam = _manifold_family(used)
-                    groups = [used] if fam is not None else [[l] for l in used]          # mixed families (e.g. "mo"): one launch per layer
-                    out, c1 = tgt, params.shape[1]
-                    for gi in range(len(groups) - 1, -1, -1):                            # last layer first, parameters sliced tail-first (:1002-1012)
-                        grp = groups[gi]
-                        f = _manifold_family(grp)
-                        if f is None:
-                            raise NotImplementedError("gradients through %s layers are not implemented" % type(grp[0]).__name__)
-                        n = sum(l.total_param_num for l in grp)
-                        # (only_last on a sphere: the last layer also takes the sphere -> plane chart, fix_euclidean_to_sphere_first, :1018-1031)
-                        structs = [l.c_struct() if f == "r" else l.c_struct(1 if (l.euclidean_to_sphere_as_first or (only_last and kind == "s")) else 0)
-                                   for l in grp]
-                        out, log_det, blp = autograd.MChainInvFn.apply(out, log_det, params[:, c1 - n:c1], base_logp if gi == 0 else None, f, structs,
-                                                                       grp[0].dimension, status)
-                        c1 -= n
-                    base_logp = blp
-            finally:
-                if stream_ctx is not None:
-                    stream_ctx.__exit__(None, None, None)
-            if stream_ctx is not None:
+            if st is not None:
                 _hip.keep_alive(out, log_det, base_logp)                  # side-stream allocations, summed / concatenated on the caller's stream
             if side is not None:
                 ld_parts.append(log_det)
@@ -1456,99 +1391,57 @@ class pdf(nn.Module):
         for si, block in enumerate(self.layer_list):
             kind = self.pdf_defs_list[si][0]
             layers = list(block)
-            fused = self._fusable_block(si, layers, only_last, amortization_parameters, x.dtype) if kind == "e" else None
-            if fused is not None and self.fused_matrix_arithmetic != "f32" and fused[0].shape[0] <= 128:
+            D = layers[0].dimension
+            ba, bb = self.base_dim_indices[si]
+            a, b = self.target_dim_indices[si]
+            cur, out_view = x[:, ba:bb], out[:, a:b]
+            route, w = self._fused_route(si, layers, kind, only_last, amortization_parameters, x)
+            res = None
+            if route == "g" and self.fused_matrix_arithmetic != "f32" and w[0].shape[0] <= 128:
                 # amortisation MLP + the g layers' solves in one launch, parameters regulated once in the MFMA result registers
                 larr = _hip.gf_layer_array([l.c_struct() for l in layers])
-                packed = self._packed_w2(si, fused[2], fused[3], larr, len(layers), layers[0].dimension, 0,
-                                         kind="split16" if self.fused_matrix_arithmetic == "split_f16" else "split")
+                packed = self._packed_w2(si, w[2], w[3], larr, len(layers), D)
                 if packed is not None:
-                    ba, bb = self.base_dim_indices[si]
-                    a, b = self.target_dim_indices[si]
-                    _, log_det = _hip.cond_gf_chain_fwd_split(self._mlp_input(si, data_summary, embeds), fused[0], fused[1], packed[1], x[:, ba:bb],
-                                                              log_det, larr, len(layers), layers[0].dimension, x_out=out[:, a:b], status=status,
-                                                              kind=packed[0])
-                    if lazy:
-                        embeds.append(block[-1]._embedding_conditional_return(out[:, a:b]))
-                    if per_block is not None:
-                        per_block.append(log_det)
-                    continue
-            lowrank = self._fusable_lowrank_block(si, layers, only_last, amortization_parameters, x) if kind == "e" else None
-            if lowrank is not None:
+                    res = _hip.cond_gf_chain_fwd_split(self._mlp_input(si, data_summary, embeds), w[0], w[1], packed[1], cur, log_det, larr,
+                                                       len(layers), D, x_out=out_view, status=status, kind=packed[0])
+            elif route == "lowrank":
                 # low-rank AmortizableMLP + the g layers' solves in one launch (float64, ranks <= 8): no (B, N) parameter block in HBM
-                ba, bb = self.base_dim_indices[si]
-                a, b = self.target_dim_indices[si]
-                res = _hip.amlp_gf_chain_fwd(_hip.as_matrix(self._mlp_input(si, data_summary, embeds)), *lowrank, x[:, ba:bb], log_det,
-                                             _hip.gf_layer_array([l.c_struct() for l in layers]), len(layers), layers[0].dimension,
-                                             x_out=out[:, a:b], status=status)
-                if res is not None:
-                    log_det = res[1]
-                    if lazy:
-                        embeds.append(block[-1]._embedding_conditional_return(out[:, a:b]))
-                    if per_block is not None:
-                        per_block.append(log_det)
-                    continue
-            mfused = self._fusable_manifold_block(si, layers, only_last, amortization_parameters, x.dtype) if kind != "e" else None
-            if mfused is not None:
+                res = _hip.amlp_gf_chain_fwd(_hip.as_matrix(self._mlp_input(si, data_summary, embeds)), *w, cur, log_det,
+                                             _hip.gf_layer_array([l.c_struct() for l in layers]), len(layers), D, x_out=out_view, status=status)
+            elif route == "m":
                 # default amortisation MLP + the manifold chain forwards in one launch: the parameter rows stay in LDS
-                fam, ws = mfused
-                structs = [l.c_struct() if fam == "r" else l.c_struct(1 if l.euclidean_to_sphere_as_first else 0) for l in layers]
-                ba, bb = self.base_dim_indices[si]
-                a, b = self.target_dim_indices[si]
-                res = _hip.cond_mchain_fwd(fam, _hip.as_matrix(self._mlp_input(si, data_summary, embeds)), *ws, x[:, ba:bb], log_det, structs,
-                                           layers[0].dimension,
-                                           x_out=out[:, a:b], status=status)
-                if res is not None:
-                    log_det = res[1]
-                    if lazy:
-                        embeds.append(block[-1]._embedding_conditional_return(out[:, a:b]))
-                    if per_block is not None:
-                        per_block.append(log_det)
-                    continue
-            extra, counter = self._block_params(si, data_summary, embeds, amortization_parameters, counter)
-            ba, bb = self.base_dim_indices[si]
-            cur = x[:, ba:bb]
-            a, b = self.target_dim_indices[si]
-            out_view = out[:, a:b]
-            if only_last:
-                if kind not in "es":
-                    raise Exception("Flow type ", kind, " does not supported *only_last*!")
-                layers = layers[-1:]
-            if kind == "e" and gfl.chain_supported(layers):
-                if extra is None:
-                    params = gfl.chain_permanent_row(layers, x)
-                elif only_last:
-                    params = extra[:, extra.shape[1] - layers[0].total_param_num:]
+                fam, ws = w
+                res = _hip.cond_mchain_fwd(fam, _hip.as_matrix(self._mlp_input(si, data_summary, embeds)), *ws, cur, log_det,
+                                           _mchain_structs(fam, layers), D, x_out=out_view, status=status)
+            if res is None:                               # (the fused launches above return None where they decline)
+                extra, counter = self._block_params(si, data_summary, embeds, amortization_parameters, counter)
+                if only_last:
+                    if kind not in "es":
+                        raise Exception("Flow type ", kind, " does not supported *only_last*!")
+                    layers = layers[-1:]
+                    extra = None if extra is None else _tail_params(extra, layers[0])
+                if kind == "e" and gfl.chain_supported(layers):
+                    res = gfl.run_chain(layers, "fwd", cur, log_det, gfl.chain_permanent_row(layers, x) if extra is None else extra, x_out=out_view,
+                                        status=status)
+                elif _manifold_family(layers) is not None:
+                    res = _manifold_chain(layers, "fwd", cur, log_det, extra, only_last and kind == "s", out_view, None, False, status)
                 else:
-                    params = extra
-                _, log_det = gfl.run_chain(layers, "fwd", cur, log_det, params, x_out=out_view, status=status)
-            elif _manifold_family(layers) is not None:
-                params = extra
-                if extra is not None and only_last:
-                    params = extra[:, extra.shape[1] - layers[0].total_param_num:]
-                _, log_det = _manifold_chain(_manifold_family(layers), layers, "fwd", cur, log_det, params, only_last and kind == "s", out_view,
-                                             None, False, status)
-            else:
-                if log_det is None:
-                    log_det = torch.zeros(B, dtype=x.dtype, device=x.device)
-                c = 0
-                groups = [[l] for l in block] if only_last else _layer_groups(list(block))
-                for gi, grp in enumerate(groups):
-                    n = sum(l.total_param_num for l in grp)
-                    this = None if extra is None else extra[:, c:c + n]
-                    c += n
-                    if only_last and gi < len(groups) - 1:
-                        continue
-                    if type(grp[0]) is gfl.gf_block and not only_last:
-                        _, log_det = gfl.run_chain(grp, "fwd", cur, log_det, this if this is not None else gfl.chain_permanent_row(grp, x),
-                                                   status=status)
-                        cur = _
-                    else:
-                        kw = {}
-                        if only_last and kind == "s":
-                            kw["fix_euclidean_to_sphere_first"] = True
-                        cur, log_det = grp[0].flow_mapping([cur, log_det], extra_inputs=this, **kw)[:2]
-                out_view.copy_(cur)
+                    if log_det is None:
+                        log_det = torch.zeros(B, dtype=x.dtype, device=x.device)
+                    c = 0
+                    for grp in _layer_groups(layers):     # head-first parameter slices
+                        n = sum(l.total_param_num for l in grp)
+                        this = None if extra is None else extra[:, c:c + n]
+                        c += n
+                        if type(grp[0]) is gfl.gf_block and not only_last:
+                            cur, log_det = gfl.run_chain(grp, "fwd", cur, log_det, this if this is not None else gfl.chain_permanent_row(grp, x),
+                                                         status=status)
+                        else:
+                            kw = {"fix_euclidean_to_sphere_first": True} if (only_last and kind == "s") else {}
+                            cur, log_det = grp[0].flow_mapping([cur, log_det], extra_inputs=this, **kw)[:2]
+                    out_view.copy_(cur)
+                    res = (out_view, log_det)
+            log_det = res[1]
             if lazy:
                 embeds.append(block[-1]._embedding_conditional_return(out_view))
             if per_block is not None:
@@ -1667,7 +1560,7 @@ class pdf(nn.Module):
         embeds = []
         with torch.no_grad():
             for si, block in enumerate(self.layer_list):
-                mlp = self.mlp_predictors[si] if len(self.mlp_predictors) > si else None
+                mlp = self._mlp(si)
                 extra = None
                 if mlp is not None:
                     pieces = []

@@ -816,7 +816,6 @@ def test_packed_image_follows_the_weights_when_the_module_dtype_differs(kernel):
     pdf = build_product(fx, torch.float64)                       # module stays float64
     arithmetic = "split_f16" if kernel == "split16" else "split_bf16"      # "split16": the default (f16 pairs on the split kernel)
     pdf.fused_matrix_arithmetic = arithmetic
-    pdf.fused_block_kernel = "auto" if kernel == "split16" else kernel
     x = to_dev(fx["x"], torch.float32)
     cond = to_dev(fx.get("cond"), torch.float32)
     pdf.check_status = False
