@@ -777,6 +777,41 @@ int jf_coverage_histogram_f64(const double* log_prob_base, int64_t B, double log
 int jf_segment_reduce_f32(const float* in, int64_t n_seg, int64_t seg_len, int32_t mode, float* out, void* stream);
 int jf_segment_reduce_f64(const double* in, int64_t n_seg, int64_t seg_len, int32_t mode, double* out, void* stream);
 
+/* jf_segment_moments: the per-group sums of pdf.marginal_moments (main/default.py:2590-3030).  x (n_seg * S, w <= 64), row stride xs;
+ *   sum_out[g, a] = sum_s x[g, s, a]; cmom_out[g, a, b] = sum_s (x[g, s, a] - mean_a)(x[g, s, b] - mean_b) (centred: sample covariance * (S - 1));
+ *   argmax_out[g] (int64) = the first s with the largest logp[g, s] -- logp and argmax_out are nullable together.  Every sum runs in a fixed
+ *   order inside the segment's own workgroup: a group's result does not depend on the other groups of the launch. */
+int jf_segment_moments_f32(const float* x, int64_t xs, const float* logp, int64_t n_seg, int64_t S, int32_t w, float* sum_out, float* cmom_out,
+                           int64_t* argmax_out, void* stream);
+int jf_segment_moments_f64(const double* x, int64_t xs, const double* logp, int64_t n_seg, int64_t S, int32_t w, double* sum_out, double* cmom_out,
+                           int64_t* argmax_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Pairwise marginal evaluation (pdf.entropy_iterative / pdf.marginal_moments; reference main/default.py:2263-2454): for n_groups groups of S
+ * samples, targets x (n_groups * S, w; default coordinates of ONE block, row stride xs) and parameter rows params (n_groups * S, P; row stride
+ * ps, or ps = 0: one permanent row for all), for the targets i in [i0, i1) of every group
+ *
+ *     out[g * S + i] = add[g * S + i] + log( 1/S * sum_j exp( logN(f^-1(x[g,i]; params[g,j])) + log_det(x[g,i]; params[g,j]) ) )
+ *
+ * add is nullable (= 0); out is the (n_groups * S) array, of which the entries [i0, i1) of every group are written.  tile: caller's scratch of
+ * n_groups * S * (i1 - i0) elements (one scalar per pair, laid out [g, j, i - i0]); the sum over j runs in the order j = 0 .. S-1 for every
+ * (g, i), so out[g, i] carries the same bits for every i-range and every number of groups.  One workgroup stages and derives ONE parameter
+ * row (g, j) in LDS -- as the broadcast regime of the chain entry points does for its single row -- and walks the group's targets against it.
+ * Solver status is reported through `status` (nullable) as the chain entry points do.
+ * jf_pair_gf: a chain of 'g' layers within the limits of the broadcast regime of jf_gf_chain_inv (D <= 64, Householder rotations, no
+ *   center_mean / add_skewness, LDS fit as jf_gf_chain_lds_bytes reports); otherwise JF_ERR_UNSUPPORTED.
+ * jf_pair_mchain: a chain of manifold layers of family fam ('r', 'o', 'm', 'f', 'v' as a character code; layers: array of the family's
+ *   jf_<fam>_layer), x in intrinsic coordinates; the limits of jf_<fam>_chain_inv ('v': float64 only); otherwise JF_ERR_UNSUPPORTED.
+ * ------------------------------------------------------------------------------------------------------------ */
+int jf_pair_gf_f32(const float* x, int64_t xs, const float* params, int64_t ps, int64_t n_groups, int32_t S, int32_t i0, int32_t i1, int32_t D,
+                   int32_t n_layers, const jf_gf_layer* layers, const float* add, float* tile, float* out, int32_t* status, void* stream);
+int jf_pair_gf_f64(const double* x, int64_t xs, const double* params, int64_t ps, int64_t n_groups, int32_t S, int32_t i0, int32_t i1, int32_t D,
+                   int32_t n_layers, const jf_gf_layer* layers, const double* add, double* tile, double* out, int32_t* status, void* stream);
+int jf_pair_mchain_f32(int32_t fam, const float* x, int64_t xs, const float* params, int64_t ps, int64_t n_groups, int32_t S, int32_t i0, int32_t i1,
+                       int32_t n_layers, const void* layers, const float* add, float* tile, float* out, int32_t* status, void* stream);
+int jf_pair_mchain_f64(int32_t fam, const double* x, int64_t xs, const double* params, int64_t ps, int64_t n_groups, int32_t S, int32_t i0, int32_t i1,
+                       int32_t n_layers, const void* layers, const double* add, double* tile, double* out, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -158,6 +158,9 @@ _SIGNATURES = {
     "jf_conditioning_rows": [ctypes.POINTER(jf_cond_segment), _I32, _I64, _P, _I64, _P],
     "jf_coverage_histogram": [_P, _I64, ctypes.c_double, _P, _I32, _P, _P, _P],
     "jf_segment_reduce": [_P, _I64, _I64, _I32, _P, _P],
+    "jf_segment_moments": [_P, _I64, _P, _I64, _I64, _I32, _P, _P, _P, _P],
+    "jf_pair_gf": [_P, _I64, _P, _I64, _I64, _I32, _I32, _I32, _I32, _I32, ctypes.POINTER(jf_gf_layer), _P, _P, _P, _P, _P],
+    "jf_pair_mchain": [_I32, _P, _I64, _P, _I64, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P],
     "jf_amlp_stage": [_P, _I64, _P, _I64, _I64, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P, _I64, _P],
     "jf_amlp_stage_bwd": [_P, _I64, _P, _I64, _I64, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P],
     "jf_t_layer_inv": [_P, _I64, _P, _P, _I64, _I32, _I64, _I32, ctypes.POINTER(jf_t_layer), _P, _I64, _P, _P, _P, _P, _P],
@@ -1569,6 +1572,75 @@ def segment_reduce(values, seg_len, mode):
     out = torch.empty((n_seg,), dtype=v.dtype, device=v.device)
     _launch("jf_segment_reduce" + _suffix(v), mode, (_ptr(v), n_seg, seg_len, {"neg_mean": 0, "logmeanexp": 1}[mode], _ptr(out)), dev)
     return out
+
+
+def segment_moments(x, seg_len, logp=None):
+    """per-segment sums of x (n_seg * seg_len, w): -> (sums (n_seg, w), centred second moments (n_seg, w, w) = sample covariance * (seg_len - 1),
+    arg-max row of logp inside each segment (n_seg,) int64, or None without logp) in one launch (jf_segment_moments)."""
+    dev = require_device(x, logp)
+    x = _rowmajor(x)
+    assert x.shape[0] % seg_len == 0
+    n_seg, w = x.shape[0] // seg_len, x.shape[1]
+    sums = torch.empty((n_seg, w), dtype=x.dtype, device=x.device)
+    cmom = torch.empty((n_seg, w, w), dtype=x.dtype, device=x.device)
+    amax = None
+    if logp is not None:
+        logp = logp.contiguous().reshape(-1)
+        if logp.dtype != x.dtype or logp.shape[0] != x.shape[0]:
+            raise ValueError("segment_moments: logp must be a (rows,) tensor of the input dtype")
+        amax = torch.empty((n_seg,), dtype=torch.int64, device=x.device)
+    _launch("jf_segment_moments" + _suffix(x), "", (_ptr(x), x.stride(0), _ptr(logp), n_seg, seg_len, w, _ptr(sums), _ptr(cmom), _ptr(amax)), dev)
+    return sums, cmom, amax
+
+
+def pair_logmeanexp(kind, x, params, n_params, n_groups, S, i0, i1, layers, dim, add=None, out=None, status=None):
+    """pairwise marginal evaluation (jf_pair_gf / jf_pair_mchain): for every group g and target i in [i0, i1)
+
+        out[g * S + i] = add[g * S + i] + log(1/S sum_j exp(log N(f^-1(x[g,i]; params[g,j])) + log_det(x[g,i]; params[g,j])))
+
+    kind: "g" (layers: a jf_gf_layer array from gf_layer_array) or a manifold family letter (layers: list of that family's structs).
+    x (n_groups * S, dim): the block's targets in default coordinates; params (n_groups * S, P) or (1, P) (one permanent row) or None (a chain
+    without parameters); n_params: the parameters the chain's layers take per row (checked against params).  `out` (n_groups * S,) is created when absent; only the entries [i0, i1) of every group are written.  Returns out, or
+    None when the library declines the chain (JF_ERR_UNSUPPORTED): the caller then takes its generic path."""
+    dev = require_device(x, params, add, out, status)
+    x = _rowmajor(x)
+    rows = n_groups * S
+    if x.shape != (rows, dim):
+        raise ValueError("pair_logmeanexp: expected targets of shape (%d, %d), got %s" % (rows, dim, tuple(x.shape)))
+    if not (0 <= i0 <= i1 <= S):
+        raise ValueError("pair_logmeanexp: bad target range [%d, %d) for S = %d" % (i0, i1, S))
+    n_layers, need = len(layers), int(n_params)
+    pptr, pstride = None, 0
+    if params is not None and params.shape[1] > 0:
+        params = _rowmajor(params)
+        if params.dtype != x.dtype:
+            raise TypeError("parameter dtype %s != input dtype %s" % (params.dtype, x.dtype))
+        if params.shape[0] not in (1, rows):
+            raise ValueError("pair_logmeanexp: parameters must have 1 or %d rows, got %d" % (rows, params.shape[0]))
+        if params.shape[1] != need:
+            raise ValueError("pair_logmeanexp: the chain takes %d parameters per row, got %d" % (need, params.shape[1]))
+        pptr, pstride = _ptr(params), (0 if params.shape[0] == 1 and rows != 1 else params.stride(0))
+    elif need != 0:
+        raise ValueError("pair_logmeanexp: the chain takes %d parameters per row, got none" % need)
+    if add is not None:
+        add = add.contiguous().reshape(-1)
+        if add.dtype != x.dtype or add.shape[0] != rows:
+            raise ValueError("pair_logmeanexp: add must be a (n_groups * S,) tensor of the input dtype")
+    if out is None:
+        out = torch.empty((rows,), dtype=x.dtype, device=x.device)
+    elif out.dtype != x.dtype or out.shape != (rows,) or not out.is_contiguous():
+        raise ValueError("pair_logmeanexp: out must be a contiguous (n_groups * S,) tensor of the input dtype")
+    tile = torch.empty((rows * (i1 - i0),), dtype=x.dtype, device=x.device)
+    suf = _suffix(x)
+    if kind == "g":
+        ok = _launch("jf_pair_gf" + suf, "pair", (_ptr(x), x.stride(0), pptr, pstride, n_groups, S, i0, i1, dim, n_layers, layers, _ptr(add),
+                                                  _ptr(tile), _ptr(out), _ptr(status)), dev, unsupported_ok=True)
+    else:
+        arr = (MCHAIN_LAYER_TYPES[kind] * n_layers)(*layers)
+        ok = _launch("jf_pair_mchain" + suf, "pair", (ord(kind), _ptr(x), x.stride(0), pptr, pstride, n_groups, S, i0, i1, n_layers,
+                                                      ctypes.cast(arr, ctypes.c_void_p), _ptr(add), _ptr(tile), _ptr(out), _ptr(status)), dev,
+                     unsupported_ok=True)
+    return out if ok else None
 
 
 def amlp_stage(x, seg, n_in, n_out, rank, has_bias, act, residual=None):

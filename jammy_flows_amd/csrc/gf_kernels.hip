@@ -560,6 +560,17 @@ static int gf_chain_fwd(const T* z, int64_t zs, const T* ld_in, const T* params,
     return launch<T, true>(a, D, bcast, ext, lds, (hipStream_t)stream);
 }
 
+// the broadcast-regime arguments of a chain (layer descriptors, LDS layout) for the pairwise kernels (pair_kernels.hip): JF_ERR_UNSUPPORTED when
+// the chain would not run as a broadcast launch of gf_chain_kernel (general options, knot tables beyond a CU's LDS)
+template <typename T> static int gf_pair_fill(GfChainArgs<T>& a, const T* params, int32_t D, int32_t n_layers, const jf_gf_layer* layers, size_t& lds) {
+    bool bcast = false, ext = false;
+    const int rc = fill_args<T>(a, params, 0, 1, 2, D, n_layers, layers, lds, bcast, ext);
+    if (rc != JF_OK) return rc;
+    return (bcast && !ext) ? JF_OK : JF_ERR_UNSUPPORTED;
+}
+int gf_pair_fill_f32(GfChainArgs<float>& a, const float* p, int32_t D, int32_t n, const jf_gf_layer* L, size_t& lds) { return gf_pair_fill<float>(a, p, D, n, L, lds); }
+int gf_pair_fill_f64(GfChainArgs<double>& a, const double* p, int32_t D, int32_t n, const jf_gf_layer* L, size_t& lds) { return gf_pair_fill<double>(a, p, D, n, L, lds); }
+
 const void* gfbg_inv_kernel_f32(int D) {
     switch (D) {
         case 2: return (const void*)gfbg_chain_inv_kernel<float, 2, 2>;
@@ -593,7 +604,7 @@ template <typename T> static int64_t gf_lds_query(int32_t D, int32_t n_layers, c
 }  // namespace jf
 
 extern "C" {
-int jf_abi_version(void) { return 8; }   // v8 (round 6): jf_get_newton_rule (which solver rule the library was built with: libjammy_hip_audit.so); v7: jf_merge_*, jf_gf_bcast_lane_rows
+int jf_abi_version(void) { return 9; }   // v9: jf_pair_gf_*, jf_pair_mchain_*, jf_segment_moments_* (marginal entropies / moments); v8 (round 6): jf_get_newton_rule (which solver rule the library was built with: libjammy_hip_audit.so); v7: jf_merge_*, jf_gf_bcast_lane_rows
 int64_t jf_gf_bcast_lane_rows(int64_t rows) {
     const int64_t prev = jf::gfbg_max_rows();
     jf::gfbg_forced_rows = rows;

@@ -38,11 +38,12 @@ template <typename T> struct GfChainArgs {
 template <int G> struct Log2 { static constexpr int v = (G == 1) ? 0 : (G == 2) ? 1 : (G == 4) ? 2 : (G == 8) ? 3 : (G == 16) ? 4 : (G == 32) ? 5 : 6; };
 
 // broadcast regime: raw rows -> LDS, then wave w derives layers w, w+4, ... (columns on lanes 0..D-1, reflections on lanes 32..)
-template <typename T> __device__ __forceinline__ void derive_broadcast(T* lds, const GfChainArgs<T>& a) {
+// `params`: the raw row to derive -- a.params for the chain kernels, the row of one (group, sample) for the pairwise kernels (pair_kernels.hip)
+template <typename T> __device__ __forceinline__ void derive_broadcast_from(T* lds, const GfChainArgs<T>& a, const T* __restrict__ params) {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     for (int l = 0; l < a.n_layers; ++l) {
         const GfLayerDev<T> o = a.L[l];
-        for (int j = tid; j < o.n_params; j += blockDim.x) lds[l * a.tile_stride + j] = a.params[o.col0 + j];
+        for (int j = tid; j < o.n_params; j += blockDim.x) lds[l * a.tile_stride + j] = params[o.col0 + j];
     }
     __syncthreads();
     for (int l = wave; l < a.n_layers; l += 4) {
@@ -58,6 +59,7 @@ template <typename T> __device__ __forceinline__ void derive_broadcast(T* lds, c
     }
     __syncthreads();
 }
+template <typename T> __device__ __forceinline__ void derive_broadcast(T* lds, const GfChainArgs<T>& a) { derive_broadcast_from<T>(lds, a, a.params); }
 
 // Broadcast regime, log-prob direction, classic stretch: lane = ROW, the row's D coordinates in registers.  Every parameter is then the same
 // for all 64 lanes of a wave: the derived (mean, 1/width, pi, pi/width) of a component come from ONE uniform 16-byte (float64: 32-byte) LDS

@@ -123,6 +123,82 @@ template <typename T> static int segment_reduce(const T* in, int64_t n_seg, int6
     return check_launch();
 }
 
+// ---- segmented moments (pdf.marginal_moments): for each segment g of S rows of x (n_seg * S, w)
+//   sum_out[g, a] = sum_s x[g, s, a]                                          (mean = sum / S; for a sphere in embedding coordinates: the resultant vector)
+//   cmom_out[g, a, b] = sum_s (x[g, s, a] - mean_a) (x[g, s, b] - mean_b)     (centred second moments: the sample covariance times S - 1)
+//   argmax_out[g] = the first s with the largest logp[g, s]                   (nullable together with logp)
+// One workgroup per segment; every sum is the workgroup's fixed tree over its 256 strided partial sums, so a segment's result does not depend
+// on the other segments of the launch.
+constexpr int SEGMOM_MAX_W = 64;
+template <typename T> __device__ __forceinline__ T segmom_block_sum(T v, T* red) {
+    const int tid = threadIdx.x;
+    red[tid] = v;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (tid < off) red[tid] += red[tid + off];
+        __syncthreads();
+    }
+    const T r = red[0];
+    __syncthreads();
+    return r;
+}
+template <typename T>
+__global__ void __launch_bounds__(256) segment_moments_kernel(const T* __restrict__ x, int64_t xs, const T* __restrict__ logp, int64_t n_seg, int64_t S,
+                                                              int w, T* __restrict__ sum_out, T* __restrict__ cmom_out, int64_t* __restrict__ argmax_out) {
+    __shared__ T red[256];
+    __shared__ T mean[SEGMOM_MAX_W];
+    __shared__ int64_t best_i[256];
+    const int64_t g = blockIdx.x;
+    const int tid = threadIdx.x;
+    const T* xg = x + g * S * xs;
+    for (int a = 0; a < w; ++a) {
+        T s = T(0);
+        for (int64_t r = tid; r < S; r += 256) s += xg[r * xs + a];
+        const T tot = segmom_block_sum<T>(s, red);
+        if (tid == 0) { sum_out[g * w + a] = tot; mean[a] = tot / T(S); }
+    }
+    __syncthreads();
+    for (int a = 0; a < w; ++a) {
+        for (int b = a; b < w; ++b) {
+            const T ma = mean[a], mb = mean[b];
+            T s = T(0);
+            for (int64_t r = tid; r < S; r += 256) s += (xg[r * xs + a] - ma) * (xg[r * xs + b] - mb);
+            const T tot = segmom_block_sum<T>(s, red);
+            if (tid == 0) { cmom_out[(g * w + a) * w + b] = tot; cmom_out[(g * w + b) * w + a] = tot; }
+        }
+    }
+    if (logp != nullptr && argmax_out != nullptr) {
+        const T* lg = logp + g * S;
+        T bv = -INFINITY;
+        int64_t bi = S;                                   // (S: no finite value seen)
+        for (int64_t r = tid; r < S; r += 256) {
+            const T v = lg[r];
+            if (v > bv || (bi == S && v == bv)) { bv = v; bi = r; }
+        }
+        red[tid] = bv; best_i[tid] = bi;
+        __syncthreads();
+        for (int off = 128; off > 0; off >>= 1) {
+            if (tid < off) {
+                const T ov = red[tid + off];
+                const int64_t oi = best_i[tid + off];
+                if (ov > red[tid] || (ov == red[tid] && oi < best_i[tid])) { red[tid] = ov; best_i[tid] = oi; }
+            }
+            __syncthreads();
+        }
+        if (tid == 0) argmax_out[g] = best_i[0] < S ? best_i[0] : 0;
+    }
+}
+template <typename T>
+static int segment_moments(const T* x, int64_t xs, const T* logp, int64_t n_seg, int64_t S, int32_t w, T* sum_out, T* cmom_out, int64_t* argmax_out,
+                           void* stream) {
+    if (!x || !sum_out || !cmom_out || n_seg < 0 || S < 1 || w < 1 || xs < w || (logp == nullptr) != (argmax_out == nullptr)) return JF_ERR_BADARG;
+    if (w > SEGMOM_MAX_W) return JF_ERR_UNSUPPORTED;
+    if (n_seg == 0) return JF_OK;
+    jf::launch(segment_moments_kernel<T>, dim3((unsigned)n_seg), dim3(256), 0, (hipStream_t)stream, x, xs, logp, n_seg, S, (int)w, sum_out, cmom_out,
+               argmax_out);
+    return check_launch();
+}
+
 template <typename T> static int normal_logp(const T* z, int64_t zs, int64_t B, int32_t D, const T* in, T* out, void* stream) {
     if (!z || !out || D < 0 || B < 0) return JF_ERR_BADARG;
     if (B == 0) return JF_OK;
@@ -405,6 +481,12 @@ int jf_segment_reduce_f32(const float* in, int64_t n_seg, int64_t seg_len, int32
 }
 int jf_segment_reduce_f64(const double* in, int64_t n_seg, int64_t seg_len, int32_t mode, double* out, void* s) {
     return jf::segment_reduce<double>(in, n_seg, seg_len, mode, out, s);
+}
+int jf_segment_moments_f32(const float* x, int64_t xs, const float* logp, int64_t n_seg, int64_t S, int32_t w, float* so, float* co, int64_t* am, void* s) {
+    return jf::segment_moments<float>(x, xs, logp, n_seg, S, w, so, co, am, s);
+}
+int jf_segment_moments_f64(const double* x, int64_t xs, const double* logp, int64_t n_seg, int64_t S, int32_t w, double* so, double* co, int64_t* am, void* s) {
+    return jf::segment_moments<double>(x, xs, logp, n_seg, S, w, so, co, am, s);
 }
 int jf_normal_logp_f32(const float* z, int64_t zs, int64_t B, int32_t D, const float* in, float* out, void* s) {
     return jf::normal_logp<float>(z, zs, B, D, in, out, s);

@@ -206,6 +206,25 @@ def _manifold_chain(layers, direction, x, log_det, extra, sphere_chart_first, x_
                        base_logp_in=base_logp_in, want_base_logp=want_base_logp, status=status, pre_ld=pre_ld, pre_blp=pre_blp)
 
 
+def _von_mises_fisher_draws(mu, kappa, n):
+    """n draws of the von-Mises(-Fisher) distribution around the unit vector mu (2 or 3 components) on the host (numpy's generator): the
+    cosine to mu by inverting its cdf (S2: closed form; S1: numpy's von-Mises sampler), the rest uniform on the circle around mu."""
+    mu = mu / numpy.linalg.norm(mu)
+    if mu.shape[0] == 2:
+        ang = numpy.arctan2(mu[1], mu[0]) + numpy.random.vonmises(0.0, kappa, size=n)
+        return numpy.stack([numpy.cos(ang), numpy.sin(ang)], axis=1)
+    u = numpy.random.uniform(size=n)
+    wz = 1.0 + numpy.log(u + (1.0 - u) * numpy.exp(-2.0 * kappa)) / kappa
+    phi = 2 * numpy.pi * numpy.random.uniform(size=n)
+    r = numpy.sqrt(numpy.clip(1.0 - wz ** 2, 0.0, None))
+    # orthonormal frame (e1, e2, mu)
+    helper_axis = numpy.array([1.0, 0.0, 0.0]) if abs(mu[0]) < 0.9 else numpy.array([0.0, 1.0, 0.0])
+    e1 = numpy.cross(mu, helper_axis)
+    e1 /= numpy.linalg.norm(e1)
+    e2 = numpy.cross(mu, e1)
+    return (r * numpy.cos(phi))[:, None] * e1[None] + (r * numpy.sin(phi))[:, None] * e2[None] + wz[:, None] * mu[None]
+
+
 class pdf(nn.Module):
     def __init__(self,
                  pdf_defs,
@@ -893,9 +912,10 @@ class pdf(nn.Module):
 
     # =========================================================================================== log-prob direction
     def _inverse_impl(self, x, log_det, data_summary, amortization_parameters, force_embedding_coordinates, force_intrinsic_coordinates,
-                      only_last, want_base_logp, status, per_block=None):
+                      only_last, want_base_logp, status, per_block=None, last_block=None):
         """`per_block` (optional list): receives the accumulated log_det after the coordinate transformation of each block (first
-        len(layer_list) entries, only when a transformation is forced) and after each block's flow -- what the marginal entropies need."""
+        len(layer_list) entries, only when a transformation is forced) and after each block's flow -- what the marginal entropies need.
+        `last_block` (with per_block): the flows of the blocks behind it are not evaluated (their base columns stay unwritten)."""
         _hip.require_device(x, log_det)
         if force_embedding_coordinates:
             assert x.shape[1] == self.total_target_dim_embedded, (x.shape[1], self.total_target_dim_embedded)
@@ -919,6 +939,7 @@ class pdf(nn.Module):
         # input alone, :946-962): each block returns its OWN log-det / base log-prob and one launch adds them up at the end
         # (_hip.combine_rows), instead of threading the running sums through the blocks as the reference does (:1020-1031).  A recorded plan
         # can then issue the blocks of a SMALL batch on side streams (csrc/plan.hip lanes): their launch / drain tails overlap.
+        assert last_block is None or per_block is not None
         independent = per_block is None and not lazy and len(self.layer_list) > 1
         ld_parts = [] if log_det is None else [log_det]
         blp_parts = []
@@ -938,6 +959,8 @@ class pdf(nn.Module):
             _hip.merge_begin()
         try:
             for si, block in enumerate(self.layer_list):      # (:998-1031)
+                if last_block is not None and si > last_block:
+                    break
                 if merge and si == 2:
                     _hip.merge_end(x)                     # the first two blocks go out as one launch; the rest follows launch by launch
                 if independent:
@@ -1718,6 +1741,333 @@ class pdf(nn.Module):
                 lp = _hip.normal_logp(base2[:, ba:bb]) + f_inc[sm] + t_inc[sm]
                 out[sm] = _hip.segment_reduce(_hip.segment_reduce(lp, S, "logmeanexp"), S, "neg_mean")
         return out
+
+    def _marginal_pair_logp(self, sm, targets, xdef, add, data_summary, batch, S, iterative_samplesize, max_iterative_batchsize, forced_emb,
+                            forced_intr, status):
+        """log p_k(x_k of sample i) for the marginal of sub-manifold sm > 0, one value per sample: the conditional density of block sm averaged
+        (log-mean-exp) over the S draws of x_<sm of the same conditional input.  The amortisation MLP of block sm sees (cond_g, embed(x_<sm of
+        sample j)) only, so its rows are computed ONCE on batch * S rows and the S x S evaluation is one pairwise launch per (group chunk,
+        i-range) (_hip.pair_logmeanexp): blocks other than sm are not evaluated at all.  Blocks the pair kernels decline take the reference's
+        own scheme (:2456-2700) on the generic path, chunked by the same two parameters."""
+        layers = list(self.layer_list[sm])
+        kind = self.pdf_defs_list[sm][0]
+        a, b = self.target_dim_indices[sm]
+        tgt = xdef[:, a:b]
+        out = torch.empty((batch * S,), dtype=xdef.dtype, device=xdef.device)
+        plan = None
+        if not self.amortize_everything:
+            fam = _manifold_family(layers)
+            if kind == "e" and gfl.chain_supported(layers):
+                plan = ("g", _hip.gf_layer_array([l.c_struct() for l in layers]), sum(l.total_param_num for l in layers))
+            elif fam is not None and not (fam == "v" and xdef.dtype != torch.float64):
+                plan = (fam, _mchain_structs(fam, layers), sum(l.total_param_num for l in layers))
+        if plan is not None:
+            embeds = self._conditioning_rows(xdef, data_summary)
+            if embeds is None:
+                embeds = [self.layer_list[p][-1]._embedding_conditional_return(xdef[:, self.target_dim_indices[p][0]:self.target_dim_indices[p][1]])
+                          for p in range(sm)]
+            extra, _ = self._block_params(sm, data_summary, embeds, None, 0)
+            if extra is None:                             # permanent parameters: one row for every pair
+                if plan[0] == "g":
+                    extra = gfl.chain_permanent_row(layers, xdef)
+                else:
+                    rows = [l._params_for(xdef, None) for l in layers]
+                    extra = torch.cat(rows, dim=1) if len(rows) > 1 else rows[0]
+            tgt_c = tgt.contiguous()
+            done = True
+            for g0 in range(0, batch, max_iterative_batchsize):
+                g1 = min(batch, g0 + max_iterative_batchsize)
+                rs = slice(g0 * S, g1 * S)
+                for i0 in range(0, S, iterative_samplesize):
+                    res = _hip.pair_logmeanexp(plan[0], tgt_c[rs], extra if extra.shape[0] == 1 else extra[rs], plan[2], g1 - g0, S, i0,
+                                               i0 + iterative_samplesize, plan[1], b - a, add=None if add is None else add[rs], out=out[rs],
+                                               status=status)
+                    if res is None:                       # the library declines this chain: every launch would
+                        done = False
+                        break
+                if not done:
+                    break
+            if done:
+                return out
+        # generic path: rows (g, i, j) = x_<sm of sample j, x_sm of sample i, later sub-manifolds filled with ones (:2413-2416)
+        dims = self.target_dims_embedded if forced_emb else (self.target_dims_intrinsic if forced_intr else self.target_dims)
+        first, w = sum(dims[:sm]), dims[sm]
+        nsub = len(self.layer_list)
+        ba, bb = self.base_dim_indices[sm]
+        tg = targets.reshape(batch, S, -1)
+        for g0 in range(0, batch, max_iterative_batchsize):
+            g1 = min(batch, g0 + max_iterative_batchsize)
+            nb = g1 - g0
+            for i0 in range(0, S, iterative_samplesize):
+                ni = iterative_samplesize
+                prev = tg[g0:g1, None, :, :first].expand(nb, ni, S, first)
+                fin = tg[g0:g1, i0:i0 + ni, None, first:first + w].expand(nb, ni, S, w)
+                fill = torch.ones((nb, ni, S, targets.shape[1] - first - w), dtype=targets.dtype, device=targets.device)
+                filled = torch.cat([prev, fin, fill], dim=3).reshape(nb * ni * S, -1)
+                ds2 = None
+                if data_summary is not None:
+                    def rep(d):
+                        return d.reshape(batch, S, -1)[g0:g1, 0].repeat_interleave(ni * S, dim=0)
+                    ds2 = [rep(d) for d in data_summary] if type(data_summary) == list else rep(data_summary)
+                marks2 = []
+                base2 = self._inverse_impl(filled, None, ds2, None, forced_emb, forced_intr, False, False, status, per_block=marks2,
+                                           last_block=sm)[0]
+
+                def inc(acc, i, start):
+                    cur = 0.0 if acc[i] is None else acc[i]
+                    prev_ = start if i == 0 else acc[i - 1]
+                    return cur - (0.0 if prev_ is None else prev_)
+                if forced_emb or forced_intr:
+                    lp = _hip.normal_logp(base2[:, ba:bb]) + inc(marks2[nsub:], sm, marks2[nsub - 1]) + inc(marks2[:nsub], sm, None)
+                else:
+                    lp = _hip.normal_logp(base2[:, ba:bb]) + inc(marks2, sm, None)
+                out.reshape(batch, S)[g0:g1, i0:i0 + ni] = _hip.segment_reduce(lp, S, "logmeanexp").reshape(nb, ni)
+        return out
+
+    def entropy_iterative(self, sub_manifolds=[-1], conditional_input=None, force_embedding_coordinates=True, force_intrinsic_coordinates=False,
+                          samplesize=100, iterative_samplesize=10, max_iterative_batchsize=20, failsafe_crosscheck_tolerance=None, dtype=None,
+                          device=None, return_samples=False, verbose=False, predefined_base=None):
+        """Monte-Carlo entropy of the pdf and of the marginal pdfs of single sub-manifolds for LARGE sample sizes (:2456-2700): the same
+        quantities as `entropy`, with memory that grows with batch * S instead of batch * S^2.  One sampling pass gives the targets and the
+        per-block log-pdfs ("total" and sub-manifold 0 are sample means of those).  For the marginal of sub-manifold k > 0 the parameter rows
+        of block k are computed once on the batch * S samples and a pairwise kernel evaluates the S targets against the S parameter rows of
+        each conditional input and reduces them by a log-mean-exp in a fixed order (csrc/pair_kernels.hip).  `iterative_samplesize` (must
+        divide `samplesize`) and `max_iterative_batchsize` bound the targets and conditional inputs per launch -- here only the scalar scratch
+        tile of batch_chunk * S * iterative_samplesize values; the results do not depend on them, bit for bit, on the kernel path.
+        Returns {"total" / index: (batch,) entropies}; with return_samples also (targets, log_pdf_dict) where log_pdf_dict holds the per-sample
+        log-pdf under "total" and every sub-manifold index (the conditional density of the block given the earlier ones), as the reference's
+        all_layer_forward_individual_subdims_incl_sampling produces.  `predefined_base` injects the standard-normal base samples (tests)."""
+        if failsafe_crosscheck_tolerance:
+            raise NotImplementedError("failsafe_crosscheck_tolerance (recheck_sampling) is outside the MI355X hot path")
+        dt, dev = self.obtain_current_dtype_n_device()
+        dev = device if device is not None else dev
+        dt = dtype if dtype is not None else dt
+        S = samplesize
+        assert samplesize % iterative_samplesize == 0, ("Sample size must be divisble by iterative sample size!", samplesize, iterative_samplesize)
+        assert max_iterative_batchsize >= 1
+        data_summary, batch = None, 1
+        if conditional_input is not None:
+            assert self.conditional_input_dim is not None
+            if type(conditional_input) == list:
+                assert len(self.conditional_input_dim) == len(conditional_input)
+                for d, ci in zip(self.conditional_input_dim, conditional_input):
+                    assert d == ci.shape[1], "Inputs of conditional input vector do not match with pre-defined input_dims!"
+                dt, dev, batch = conditional_input[0].dtype, conditional_input[0].device, conditional_input[0].shape[0]
+                data_summary = [ci.repeat_interleave(S, dim=0) for ci in conditional_input]
+            else:
+                dt, dev, batch = conditional_input.dtype, conditional_input.device, conditional_input.shape[0]
+                data_summary = conditional_input.repeat_interleave(S, dim=0)
+        else:
+            assert self.conditional_input_dim is None, "We require conditional input, since this is a conditional PDF."
+        if not force_embedding_coordinates:
+            print("#### CAUTION: Calculating entropy without forcing embedding coordinates. This might lead to undesired and wrong entropies "
+                  "when using manifold PDFs!#############")
+        for sm in sub_manifolds:
+            assert sm == -1 or 0 <= sm < len(self.layer_list)
+        nsub = len(self.layer_list)
+        out = {}
+        with torch.no_grad():
+            z = predefined_base if predefined_base is not None else torch.randn((S * batch, self.total_base_dim), dtype=dt, device=dev)
+            assert z.shape == (S * batch, self.total_base_dim)
+            status = _hip.new_status(z.device) if self.check_status else None
+            marks = []
+            targets, log_det = self.all_layer_forward(z, None, data_summary, force_embedding_coordinates=force_embedding_coordinates,
+                                                      force_intrinsic_coordinates=force_intrinsic_coordinates, status=status, per_block=marks)
+            forced = force_embedding_coordinates or force_intrinsic_coordinates
+
+            def increments(acc, start):
+                res, prev = [], start
+                for m in acc:
+                    cur = 0.0 if m is None else m
+                    res.append(cur - (0.0 if prev is None else prev))
+                    prev = m
+                return res
+            flow_inc = increments(marks[:nsub], None)
+            trans_inc = increments(marks[nsub:], marks[nsub - 1]) if forced else [0.0] * nsub
+            log_pdf_dict = {"total": _hip.normal_logp(z) - log_det}
+            if return_samples or 0 in sub_manifolds:
+                for si in range(nsub if return_samples else 1):
+                    ba, bb = self.base_dim_indices[si]
+                    log_pdf_dict[si] = _hip.normal_logp(z[:, ba:bb]) - (flow_inc[si] + trans_inc[si])
+            xdef = back_inc = None
+            for sm in sub_manifolds:
+                if verbose:
+                    print("---> calculating entropy for index ", sm)
+                if sm == -1:
+                    out["total"] = _hip.segment_reduce(log_pdf_dict["total"], S, "neg_mean")
+                elif sm == 0:
+                    out[0] = _hip.segment_reduce(log_pdf_dict[0], S, "neg_mean")
+                else:
+                    if xdef is None:                      # the targets in default coordinates, once; block k's log-det alone is its addend
+                        if forced:
+                            back = []
+                            xdef, _ = self.transform_target_space(targets, None, transform_from="embedding" if force_embedding_coordinates else "intrinsic",
+                                                                  transform_to="default", per_block=back)
+                            back_inc = increments(back, None)
+                        else:
+                            xdef, back_inc = targets, [0.0] * nsub
+                    add = back_inc[sm] if isinstance(back_inc[sm], torch.Tensor) else None
+                    lp = self._marginal_pair_logp(sm, targets, xdef, add, data_summary, batch, S, iterative_samplesize, max_iterative_batchsize,
+                                                  force_embedding_coordinates, force_intrinsic_coordinates, status)
+                    out[sm] = _hip.segment_reduce(lp, S, "neg_mean")
+            self._report_status(status)
+        if return_samples:
+            return out, targets, log_pdf_dict
+        return out
+
+    def marginal_moments(self, conditional_input=None, samplesize=50, iterative_samplesize=10, max_iterative_batchsize=20, mises_abs_precision=1e-7,
+                         calc_kl_diff_and_entropic_quantities=False, failsafe_crosscheck_tolerance=None, dtype=None, device=None, verbose=False,
+                         s2_entropy_scanning=False, s2_entropy_scan_nside=32, return_samples=False, predefined_base=None):
+        """First and second moments of the marginal distribution of every sub-manifold from `samplesize` samples per conditional input
+        (:3290-3960): a Gaussian approximation for Euclidean sub-manifolds (mean_k, varlike_k = sample covariance, approx_entropy_k), a
+        von-Mises(-Fisher) approximation for S1 / S2 (mean_k = resultant direction, mean_k_angles, varlike_k = concentration kappa from the
+        reference's Newton iteration, approx_entropy_k; S2 also azivar_k / zenvar_k), the sample of largest log-pdf (argmax_k[_angles]) and,
+        with return_samples, samples_k[_angles].  With calc_kl_diff_and_entropic_quantities also entropy_k / entropy_total (entropy_iterative
+        on the same samples), cross_entropy_k = -mean log q_k(samples) for the fitted approximation q_k, kl_diff_exact_approx_k =
+        cross_entropy_k - entropy_k, and for k = 0 reverse_cross_entropy_0 / kl_diff_approx_exact_0 from draws of the fit.  Sampling, the
+        per-group sums (jf_segment_moments) and the entropies run on the device; every returned array is copied to the host once.
+        `predefined_base` injects the standard-normal base samples (tests).
+        Not provided: s2_entropy_scanning (needs healpy: NotImplementedError) and the reference's zlp_kent_* keys (its Kent fit is an
+        optimiser of its own, outside this method).  S1 uses log c = -log(2 pi I0(kappa)) (the reference's S1 branch never assigns it)."""
+        from scipy import special
+        if failsafe_crosscheck_tolerance:
+            raise NotImplementedError("failsafe_crosscheck_tolerance (recheck_sampling) is outside the MI355X hot path")
+        if s2_entropy_scanning:
+            raise NotImplementedError("s2_entropy_scanning needs healpy and is not provided")
+        dt, dev = self.obtain_current_dtype_n_device()
+        dev = device if device is not None else dev
+        dt = dtype if dtype is not None else dt
+        S = samplesize
+        batch, data_summary = 1, None
+        if conditional_input is not None:
+            first = conditional_input[0] if type(conditional_input) == list else conditional_input
+            batch, dt, dev = first.shape[0], first.dtype, first.device
+            data_summary = ([ci.repeat_interleave(S, dim=0) for ci in conditional_input] if type(conditional_input) == list
+                            else conditional_input.repeat_interleave(S, dim=0))
+        for d in self.pdf_defs_list:
+            if not ("e" in d or "s" in d):
+                raise Exception("Unsupported sub pdf type for marginal moment calculation!", d)
+        ret = {}
+        entropy_dict = None
+        if calc_kl_diff_and_entropic_quantities:
+            # (before the embedding flags are switched: exactly the caller's own entropy_iterative call, samples in embedding coordinates)
+            entropy_dict, samples, log_pdf_dict = self.entropy_iterative(
+                sub_manifolds=[-1] + list(range(len(self.pdf_defs_list))), conditional_input=conditional_input, samplesize=S,
+                iterative_samplesize=iterative_samplesize, max_iterative_batchsize=max_iterative_batchsize, device=dev, dtype=dt,
+                return_samples=True, verbose=verbose, predefined_base=predefined_base)
+            logp = log_pdf_dict["total"]
+        previous_flags = self.get_embedding_flags()
+        self.set_embedding_flags(True)
+        try:
+            with torch.no_grad():
+                if entropy_dict is None:
+                    samples, _, logp, _ = self._obtain_sample(conditional_input=data_summary, predefined_target_input=predefined_base,
+                                                              samplesize=S, force_embedding_coordinates=True, dtype=dt, device=dev)
+                assert samples.shape == (batch * S, self.total_target_dim_embedded)
+                host = lambda t: t.cpu().numpy()
+                rows = torch.arange(batch, device=samples.device) * S
+                for k, pdef in enumerate(self.pdf_defs_list):
+                    a, b = self.target_dim_indices_embedded[k]
+                    sub = samples[:, a:b]
+                    w = b - a
+                    sums, cmom, amax = _hip.segment_moments(sub, S, logp)
+                    arg_max = sub[rows + amax]
+                    if return_samples:
+                        ret["samples_%d" % k] = host(sub.reshape(batch, S, w))
+                    cross = None
+                    if "e" in pdef:
+                        mean = sums / S
+                        var = cmom / (S - 1)
+                        approx = 0.5 * (w * (numpy.log(2 * numpy.pi) + 1) + torch.log(torch.linalg.det(var)))
+                        if entropy_dict is not None:
+                            # -mean log N(x; mean, var) = 0.5 (w log 2 pi + log det var + tr(var^-1 C) / S),  C = centred second moments
+                            tr = (torch.linalg.inv(var) * cmom).sum(dim=(1, 2)) / S
+                            cross = 0.5 * (w * numpy.log(2 * numpy.pi) + torch.log(torch.linalg.det(var)) + tr)
+                            if k == 0:
+                                draws = torch.distributions.MultivariateNormal(mean, covariance_matrix=var).sample(sample_shape=(S,))
+                                draws = draws.transpose(0, 1).reshape(batch * S, w).to(samples)
+                        varlike = var
+                    else:
+                        layer0 = self.layer_list[k][0]
+                        length = (sums ** 2).sum(dim=1, keepdim=True).sqrt()
+                        mean = sums / length
+                        ang_mean, _ = layer0.eucl_to_spherical_embedding(mean, 0.0)
+                        ang, _ = layer0.eucl_to_spherical_embedding(sub, 0.0)
+                        if return_samples:
+                            ret["samples_%d_angles" % k] = host(ang.reshape(batch, S, w - 1))
+                        ret["argmax_%d_angles" % k] = host(layer0.eucl_to_spherical_embedding(arg_max, 0.0)[0])
+                        ret["mean_%d_angles" % k] = host(ang_mean)
+                        R = length / S
+                        p = w
+                        if p == 3:
+                            angs = ang.reshape(batch, S, 2)
+                            azi = angs[..., 1] - ang_mean[:, None, 1]
+                            azi = torch.where(azi < 0, azi + 2 * numpy.pi, azi)
+                            azi = torch.where(azi >= numpy.pi, azi - 2 * numpy.pi, azi)
+                            ret["azivar_%d" % k] = numpy.var(host(azi), axis=-1)
+                            ret["zenvar_%d" % k] = numpy.var(host(angs[..., 0]), axis=1)
+                        # kappa: the reference's Newton iteration on A_p(kappa) = R (batch scalars, on the host as there)
+                        Rc = host(R).astype(numpy.float64)
+                        kap = Rc * (p - Rc ** 2) / (1 - Rc ** 2)
+                        for _ in range(20):
+                            if p == 2:
+                                apk = special.i1(kap) / special.i0(kap)
+                                new = kap - (apk - Rc) / (1.0 - apk ** 2 - (1.0 / kap) * apk)
+                            else:
+                                apk = -1.0 / kap + 1.0 / numpy.tanh(kap)
+                                new = kap - (apk - Rc) / (1.0 - apk ** 2 - (2.0 / kap) * apk)
+                            diff = numpy.abs(new - kap).max()
+                            kap = new
+                            if diff < mises_abs_precision:
+                                break
+                        if p == 2:
+                            apk = special.i1(kap) / special.i0(kap)
+                            log_c = -numpy.log(2 * numpy.pi) - (numpy.log(special.i0e(kap)) + kap)
+                        else:
+                            apk = -1.0 / kap + 1.0 / numpy.tanh(kap)
+                            log_c = numpy.log(kap) - numpy.log(2 * numpy.pi) - (kap + numpy.log1p(-numpy.exp(-2 * kap)))
+                        kappa = torch.from_numpy(kap).to(mean)
+                        log_c_t = torch.from_numpy(log_c).to(mean)
+                        approx = (-log_c_t - kappa * torch.from_numpy(apk).to(mean)).squeeze(1)
+                        if entropy_dict is not None:
+                            # -mean log q = -(kappa <mean, sum x> / S + log c)
+                            cross = -((mean * sums).sum(dim=1) * kappa.squeeze(1) / S + log_c_t.squeeze(1))
+                            if k == 0:
+                                draws = torch.from_numpy(numpy.concatenate([_von_mises_fisher_draws(host(mean[g]).astype(numpy.float64), float(kap[g, 0]), S)
+                                                                            for g in range(batch)], axis=0)).to(samples)
+                        varlike = kappa
+                    ret["mean_%d" % k] = host(mean)
+                    ret["argmax_%d" % k] = host(arg_max)
+                    ret["varlike_%d" % k] = host(varlike)
+                    if entropy_dict is not None:
+                        ret["entropy_%d" % k] = host(entropy_dict[k])
+                        ret["cross_entropy_%d" % k] = host(cross)
+                        ret["kl_diff_exact_approx_%d" % k] = host(cross - entropy_dict[k])
+                        if k == 0:
+                            # reverse direction: draws of the fitted approximation, scored by the pdf's first sub-manifold marginal
+                            rev = self._first_marginal_logp(draws, data_summary)
+                            rce = _hip.segment_reduce(rev, S, "neg_mean")
+                            ret["reverse_cross_entropy_0"] = host(rce)
+                            ret["kl_diff_approx_exact_0"] = host(rce - approx)
+                    ret["approx_entropy_%d" % k] = host(approx)
+                if entropy_dict is not None:
+                    ret["entropy_total"] = host(entropy_dict["total"])
+        finally:
+            for i, f in enumerate(previous_flags):
+                self.set_embedding_flags(f, sub_pdf_index=i)
+        return ret
+
+    def _first_marginal_logp(self, x0, data_summary):
+        """log-pdf of the first sub-manifold's marginal at x0 (embedding coordinates): block 0 depends on the conditional input alone, so the
+        later blocks are filled with ones and only block 0's base log-prob and log-det are kept (as the marginal entropies do)."""
+        nsub = len(self.layer_list)
+        fill = torch.ones((x0.shape[0], self.total_target_dim_embedded - x0.shape[1]), dtype=x0.dtype, device=x0.device)
+        marks = []
+        base = self._inverse_impl(torch.cat([x0, fill], dim=1), None, data_summary, None, True, False, False, False, None, per_block=marks)[0]
+        ba, bb = self.base_dim_indices[0]
+        t0 = 0.0 if marks[0] is None else marks[0]
+        f0 = (0.0 if marks[nsub] is None else marks[nsub]) - (0.0 if marks[nsub - 1] is None else marks[nsub - 1])
+        return _hip.normal_logp(base[:, ba:bb]) + f0 + t0
 
     # =========================================================================================== coordinate systems
     def transform_target_into_returnable_params(self, target):
