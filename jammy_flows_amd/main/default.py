@@ -225,6 +225,102 @@ def _von_mises_fisher_draws(mu, kappa, n):
     return (r * numpy.cos(phi))[:, None] * e1[None] + (r * numpy.sin(phi))[:, None] * e2[None] + wz[:, None] * mu[None]
 
 
+def _block_log_dets(marks, nsub, forced, flow_first):
+    """per-block log-det increments (flow, trans) from the marks a `per_block` list collects.  A mark is the log-det ACCUMULATED so far (None:
+    nothing added yet), so an increment is the difference of two neighbours of the whole list.  The nsub marks of the coordinate
+    transformation exist only when one is `forced` (else trans is all 0.0): they stand before the flow marks in the log-prob direction and
+    behind them in the sampling direction (`flow_first`).  `last_block` shortens the flow part; transform_target_space alone leaves it
+    empty."""
+    steps, prev = [], None
+    for m in marks:
+        steps.append((0.0 if m is None else m) - (0.0 if prev is None else prev))
+        prev = m
+    if not forced:
+        return steps, [0.0] * nsub
+    return (steps[:nsub], steps[nsub:]) if flow_first else (steps[nsub:], steps[:nsub])
+
+
+def _host(t):
+    return t.cpu().numpy()
+
+
+def _gaussian_fit(sub, sums, cmom, S, want_cross, want_draws):
+    """Gaussian approximation of a Euclidean sub-manifold from the per-group sums and centred second moments of its samples `sub`
+    -> (mean, covariance, approx entropy, cross entropy -mean log q(samples) or None, S draws of the fit per group (torch's generator) or None)"""
+    w = sub.shape[1]
+    mean = sums / S
+    var = cmom / (S - 1)
+    approx = 0.5 * (w * (numpy.log(2 * numpy.pi) + 1) + torch.log(torch.linalg.det(var)))
+    cross = draws = None
+    if want_cross:
+        # -mean log N(x; mean, var) = 0.5 (w log 2 pi + log det var + tr(var^-1 C) / S),  C = centred second moments
+        tr = (torch.linalg.inv(var) * cmom).sum(dim=(1, 2)) / S
+        cross = 0.5 * (w * numpy.log(2 * numpy.pi) + torch.log(torch.linalg.det(var)) + tr)
+    if want_draws:
+        draws = torch.distributions.MultivariateNormal(mean, covariance_matrix=var).sample(sample_shape=(S,))
+        draws = draws.transpose(0, 1).reshape(mean.shape[0] * S, w).to(sub)
+    return mean, var, approx, cross, draws
+
+
+def _vmf_mean_resultant(p, kappa):
+    """A_p(kappa): the mean resultant length of the von-Mises(-Fisher) distribution on S1 (p = 2) / S2 (p = 3)"""
+    from scipy import special
+    return special.i1(kappa) / special.i0(kappa) if p == 2 else -1.0 / kappa + 1.0 / numpy.tanh(kappa)
+
+
+def _vmf_log_c(p, kappa):
+    """log of its normalisation: 1 / (2 pi I0(kappa)) on S1, kappa / (4 pi sinh kappa) on S2"""
+    from scipy import special
+    if p == 2:
+        return -numpy.log(2 * numpy.pi) - (numpy.log(special.i0e(kappa)) + kappa)
+    return numpy.log(kappa) - numpy.log(2 * numpy.pi) - (kappa + numpy.log1p(-numpy.exp(-2 * kappa)))
+
+
+def _vmf_fit(layer0, sub, sums, arg_max, S, abs_precision, want_cross, want_draws, want_samples):
+    """von-Mises(-Fisher) approximation of an S1 / S2 sub-manifold from the per-group sums of its samples `sub` (embedding coordinates)
+    -> (mean direction, kappa, approx entropy, cross entropy or None, S draws of the fit per group (numpy's global generator, group by group)
+    or None, {key pattern: host array} of the angle and azivar / zenvar entries)"""
+    batch, p = sums.shape[0], sub.shape[1]
+    length = (sums ** 2).sum(dim=1, keepdim=True).sqrt()
+    mean = sums / length
+    ang_mean, _ = layer0.eucl_to_spherical_embedding(mean, 0.0)
+    ang, _ = layer0.eucl_to_spherical_embedding(sub, 0.0)
+    entries = {}
+    if want_samples:
+        entries["samples_%d_angles"] = _host(ang.reshape(batch, S, p - 1))
+    entries["argmax_%d_angles"] = _host(layer0.eucl_to_spherical_embedding(arg_max, 0.0)[0])
+    entries["mean_%d_angles"] = _host(ang_mean)
+    if p == 3:
+        angs = ang.reshape(batch, S, 2)
+        azi = angs[..., 1] - ang_mean[:, None, 1]
+        azi = torch.where(azi < 0, azi + 2 * numpy.pi, azi)
+        azi = torch.where(azi >= numpy.pi, azi - 2 * numpy.pi, azi)
+        entries["azivar_%d"] = numpy.var(_host(azi), axis=-1)
+        entries["zenvar_%d"] = numpy.var(_host(angs[..., 0]), axis=1)
+    # kappa: the reference's Newton iteration on A_p(kappa) = R (batch scalars, on the host as there)
+    Rc = _host(length / S).astype(numpy.float64)
+    kap = Rc * (p - Rc ** 2) / (1 - Rc ** 2)
+    for _ in range(20):
+        apk = _vmf_mean_resultant(p, kap)
+        new = kap - (apk - Rc) / (1.0 - apk ** 2 - ((p - 1.0) / kap) * apk)
+        diff = numpy.abs(new - kap).max()
+        kap = new
+        if diff < abs_precision:
+            break
+    log_c = _vmf_log_c(p, kap)
+    kappa = torch.from_numpy(kap).to(mean)
+    log_c_t = torch.from_numpy(log_c).to(mean)
+    approx = (-log_c_t - kappa * torch.from_numpy(_vmf_mean_resultant(p, kap)).to(mean)).squeeze(1)
+    cross = draws = None
+    if want_cross:
+        # -mean log q = -(kappa <mean, sum x> / S + log c)
+        cross = -((mean * sums).sum(dim=1) * kappa.squeeze(1) / S + log_c_t.squeeze(1))
+    if want_draws:
+        draws = torch.from_numpy(numpy.concatenate([_von_mises_fisher_draws(_host(mean[g]).astype(numpy.float64), float(kap[g, 0]), S)
+                                                    for g in range(batch)], axis=0)).to(sub)
+    return mean, kappa, approx, cross, draws, entries
+
+
 class pdf(nn.Module):
     def __init__(self,
                  pdf_defs,
@@ -1658,6 +1754,42 @@ class pdf(nn.Module):
                 ret["true"][key], ret["logprob_diffs"][key], ret["chi2_cdf_evals"][key] = t, d, c
         return ret
 
+    def _repeat_conditional(self, conditional_input, S, dtype, device):
+        """set-up of entropy / entropy_iterative / marginal_moments -> (dtype, device, batch, data_summary): the conditional input checked
+        against the pdf's definition, each of its rows repeated S times; dtype and device follow it where there is one."""
+        dt, dev = self.obtain_current_dtype_n_device()
+        dev = device if device is not None else dev
+        dt = dtype if dtype is not None else dt
+        if conditional_input is None:
+            assert self.conditional_input_dim is None, "We require conditional input, since this is a conditional PDF."
+            return dt, dev, 1, None
+        assert self.conditional_input_dim is not None
+        is_list = type(conditional_input) == list
+        if is_list:
+            assert len(self.conditional_input_dim) == len(conditional_input)
+            for d, ci in zip(self.conditional_input_dim, conditional_input):
+                assert d == ci.shape[1], "Inputs of conditional input vector do not match with pre-defined input_dims!"
+        first = conditional_input[0] if is_list else conditional_input
+        repeated = [ci.repeat_interleave(S, dim=0) for ci in (conditional_input if is_list else [conditional_input])]
+        return first.dtype, first.device, first.shape[0], repeated if is_list else repeated[0]
+
+    def _sampling_pass(self, predefined_base, rows, dt, dev, data_summary, forced_emb, forced_intr, blocks):
+        """one pass in the sampling direction on `rows` base samples (drawn here unless injected) -> (targets, per-sample log-pdfs, status):
+        the log-pdfs under "total" and, for each index in `blocks`, the conditional density of that block given the earlier ones.  The status
+        words are the caller's to report."""
+        z = predefined_base if predefined_base is not None else torch.randn((rows, self.total_base_dim), dtype=dt, device=dev)
+        assert z.shape == (rows, self.total_base_dim)
+        status = _hip.new_status(z.device) if self.check_status else None
+        marks = []
+        targets, log_det = self.all_layer_forward(z, None, data_summary, force_embedding_coordinates=forced_emb,
+                                                  force_intrinsic_coordinates=forced_intr, status=status, per_block=marks)
+        flow, trans = _block_log_dets(marks, len(self.layer_list), forced_emb or forced_intr, True)
+        log_pdfs = {"total": _hip.normal_logp(z) - log_det}
+        for si in blocks:
+            ba, bb = self.base_dim_indices[si]
+            log_pdfs[si] = _hip.normal_logp(z[:, ba:bb]) - (flow[si] + trans[si])
+        return targets, log_pdfs, status
+
     def entropy(self, sub_manifolds=[-1], conditional_input=None, force_embedding_coordinates=True, force_intrinsic_coordinates=False,
                 samplesize=100, failsafe_crosscheck_tolerance=None, dtype=None, device=None, predefined_base=None):
         """Monte-Carlo entropy of the pdf and of the marginal pdfs of single sub-manifolds (:2263-2454): -mean log p over `samplesize`
@@ -1666,140 +1798,84 @@ class pdf(nn.Module):
         sample means (jf_segment_reduce) all stay on the device.  `predefined_base` injects the standard-normal base samples (tests)."""
         if failsafe_crosscheck_tolerance:
             raise NotImplementedError("failsafe_crosscheck_tolerance (recheck_sampling) is outside the MI355X hot path")
-        dt, dev = self.obtain_current_dtype_n_device()
-        dev = device if device is not None else dev
-        dt = dtype if dtype is not None else dt
         S = samplesize
-        data_summary, batch = None, 1
-        if conditional_input is not None:
-            assert self.conditional_input_dim is not None
-            if type(conditional_input) == list:
-                dt, dev, batch = conditional_input[0].dtype, conditional_input[0].device, conditional_input[0].shape[0]
-                data_summary = [ci.repeat_interleave(S, dim=0) for ci in conditional_input]
-            else:
-                dt, dev, batch = conditional_input.dtype, conditional_input.device, conditional_input.shape[0]
-                data_summary = conditional_input.repeat_interleave(S, dim=0)
-        else:
-            assert self.conditional_input_dim is None, "We require conditional input, since this is a conditional PDF."
+        dt, dev, batch, data_summary = self._repeat_conditional(conditional_input, S, dtype, device)
         for sm in sub_manifolds:
             assert sm == -1 or 0 <= sm < len(self.layer_list)
-        nsub = len(self.layer_list)
         out = {}
         with torch.no_grad():
-            z = predefined_base if predefined_base is not None else torch.randn((S * batch, self.total_base_dim), dtype=dt, device=dev)
-            assert z.shape == (S * batch, self.total_base_dim)
-            status = _hip.new_status(z.device) if self.check_status else None
-            marks = []
-            targets, log_det = self.all_layer_forward(z, None, data_summary, force_embedding_coordinates=force_embedding_coordinates,
-                                                      force_intrinsic_coordinates=force_intrinsic_coordinates, status=status, per_block=marks)
+            targets, log_pdfs, status = self._sampling_pass(predefined_base, S * batch, dt, dev, data_summary, force_embedding_coordinates,
+                                                            force_intrinsic_coordinates, [0] if 0 in sub_manifolds else [])
             self._report_status(status)
-            forced = force_embedding_coordinates or force_intrinsic_coordinates
-
-            def increments(acc, start):
-                """accumulated log-dets (None = nothing added yet) -> per-block increments"""
-                res, prev = [], start
-                for m in acc:
-                    cur = 0.0 if m is None else m
-                    res.append(cur - (0.0 if prev is None else prev))
-                    prev = m
-                return res
-            # sampling direction: flow marks first, then (if forced) the marks of the coordinate transformation
-            flow_inc = increments(marks[:nsub], None)
-            trans_inc = increments(marks[nsub:], marks[nsub - 1]) if forced else [0.0] * nsub
             if -1 in sub_manifolds:
-                out["total"] = _hip.segment_reduce(_hip.normal_logp(z) - log_det, S, "neg_mean")
+                out["total"] = _hip.segment_reduce(log_pdfs["total"], S, "neg_mean")
             for sm in sub_manifolds:
-                if sm == -1:
-                    continue
-                ba, bb = self.base_dim_indices[sm]
                 if sm == 0:
-                    out[0] = _hip.segment_reduce(_hip.normal_logp(z[:, ba:bb]) - (flow_inc[0] + trans_inc[0]), S, "neg_mean")
-                    continue
-                dims = self.target_dims_embedded if force_embedding_coordinates else (
-                    self.target_dims_intrinsic if force_intrinsic_coordinates else self.target_dims)
-                first = sum(dims[:sm])
-                w = dims[sm]
-                # rows (g, i, j): x_<k of sample j, x_k of sample i of conditional input g; later sub-manifolds filled with ones (:2413-2416)
-                tg = targets.reshape(batch, S, -1)
-                prev = tg[:, None, :, :first].expand(batch, S, S, first)
-                fin = tg[:, :, None, first:first + w].expand(batch, S, S, w)
-                fill = torch.ones((batch, S, S, targets.shape[1] - first - w), dtype=targets.dtype, device=targets.device)
-                filled = torch.cat([prev, fin, fill], dim=3).reshape(batch * S * S, -1)
-                ds2 = None
-                if data_summary is not None:
-                    ds2 = ([d.repeat_interleave(S, dim=0) for d in data_summary] if type(data_summary) == list
-                           else data_summary.repeat_interleave(S, dim=0))
-                marks2 = []
-                base2, _, _, _ = self._inverse_impl(filled, None, ds2, None, force_embedding_coordinates, force_intrinsic_coordinates, False, False, None,
-                                                 per_block=marks2)
-                # log-prob direction: (if forced) transformation marks first, then the flow marks continuing from their total
-                if forced:
-                    t_inc = increments(marks2[:nsub], None)
-                    f_inc = increments(marks2[nsub:], marks2[nsub - 1])
-                else:
-                    t_inc, f_inc = [0.0] * nsub, increments(marks2, None)
-                lp = _hip.normal_logp(base2[:, ba:bb]) + f_inc[sm] + t_inc[sm]
-                out[sm] = _hip.segment_reduce(_hip.segment_reduce(lp, S, "logmeanexp"), S, "neg_mean")
+                    out[0] = _hip.segment_reduce(log_pdfs[0], S, "neg_mean")
+                elif sm > 0:
+                    # the S x S rows of every conditional input as ONE chunk of the generic pass, without status words
+                    lp = self._generic_pair_logp(sm, targets, data_summary, batch, S, S, max(batch, 1), force_embedding_coordinates,
+                                                 force_intrinsic_coordinates, None)
+                    out[sm] = _hip.segment_reduce(lp, S, "neg_mean")
         return out
 
-    def _marginal_pair_logp(self, sm, targets, xdef, add, data_summary, batch, S, iterative_samplesize, max_iterative_batchsize, forced_emb,
-                            forced_intr, status):
+    def _kernel_pair_logp(self, sm, xdef, add, data_summary, batch, S, iterative_samplesize, max_iterative_batchsize, status):
         """log p_k(x_k of sample i) for the marginal of sub-manifold sm > 0, one value per sample: the conditional density of block sm averaged
         (log-mean-exp) over the S draws of x_<sm of the same conditional input.  The amortisation MLP of block sm sees (cond_g, embed(x_<sm of
         sample j)) only, so its rows are computed ONCE on batch * S rows and the S x S evaluation is one pairwise launch per (group chunk,
-        i-range) (_hip.pair_logmeanexp): blocks other than sm are not evaluated at all.  Blocks the pair kernels decline take the reference's
-        own scheme (:2456-2700) on the generic path, chunked by the same two parameters."""
+        i-range) (_hip.pair_logmeanexp): blocks other than sm are not evaluated at all.  None: the pair kernels decline this block (the caller
+        takes _generic_pair_logp)."""
         layers = list(self.layer_list[sm])
         kind = self.pdf_defs_list[sm][0]
         a, b = self.target_dim_indices[sm]
-        tgt = xdef[:, a:b]
+        if self.amortize_everything:
+            return None
+        fam = _manifold_family(layers)
+        if kind == "e" and gfl.chain_supported(layers):
+            plan = ("g", _hip.gf_layer_array([l.c_struct() for l in layers]), sum(l.total_param_num for l in layers))
+        elif fam is not None and not (fam == "v" and xdef.dtype != torch.float64):
+            plan = (fam, _mchain_structs(fam, layers), sum(l.total_param_num for l in layers))
+        else:
+            return None
+        embeds = self._conditioning_rows(xdef, data_summary)
+        if embeds is None:
+            embeds = [self.layer_list[p][-1]._embedding_conditional_return(xdef[:, self.target_dim_indices[p][0]:self.target_dim_indices[p][1]])
+                      for p in range(sm)]
+        extra, _ = self._block_params(sm, data_summary, embeds, None, 0)
+        if extra is None:                                 # permanent parameters: one row for every pair
+            if plan[0] == "g":
+                extra = gfl.chain_permanent_row(layers, xdef)
+            else:
+                rows = [l._params_for(xdef, None) for l in layers]
+                extra = torch.cat(rows, dim=1) if len(rows) > 1 else rows[0]
+        tgt_c = xdef[:, a:b].contiguous()
         out = torch.empty((batch * S,), dtype=xdef.dtype, device=xdef.device)
-        plan = None
-        if not self.amortize_everything:
-            fam = _manifold_family(layers)
-            if kind == "e" and gfl.chain_supported(layers):
-                plan = ("g", _hip.gf_layer_array([l.c_struct() for l in layers]), sum(l.total_param_num for l in layers))
-            elif fam is not None and not (fam == "v" and xdef.dtype != torch.float64):
-                plan = (fam, _mchain_structs(fam, layers), sum(l.total_param_num for l in layers))
-        if plan is not None:
-            embeds = self._conditioning_rows(xdef, data_summary)
-            if embeds is None:
-                embeds = [self.layer_list[p][-1]._embedding_conditional_return(xdef[:, self.target_dim_indices[p][0]:self.target_dim_indices[p][1]])
-                          for p in range(sm)]
-            extra, _ = self._block_params(sm, data_summary, embeds, None, 0)
-            if extra is None:                             # permanent parameters: one row for every pair
-                if plan[0] == "g":
-                    extra = gfl.chain_permanent_row(layers, xdef)
-                else:
-                    rows = [l._params_for(xdef, None) for l in layers]
-                    extra = torch.cat(rows, dim=1) if len(rows) > 1 else rows[0]
-            tgt_c = tgt.contiguous()
-            done = True
-            for g0 in range(0, batch, max_iterative_batchsize):
-                g1 = min(batch, g0 + max_iterative_batchsize)
-                rs = slice(g0 * S, g1 * S)
-                for i0 in range(0, S, iterative_samplesize):
-                    res = _hip.pair_logmeanexp(plan[0], tgt_c[rs], extra if extra.shape[0] == 1 else extra[rs], plan[2], g1 - g0, S, i0,
-                                               i0 + iterative_samplesize, plan[1], b - a, add=None if add is None else add[rs], out=out[rs],
-                                               status=status)
-                    if res is None:                       # the library declines this chain: every launch would
-                        done = False
-                        break
-                if not done:
-                    break
-            if done:
-                return out
-        # generic path: rows (g, i, j) = x_<sm of sample j, x_sm of sample i, later sub-manifolds filled with ones (:2413-2416)
+        for g0 in range(0, batch, max_iterative_batchsize):
+            g1 = min(batch, g0 + max_iterative_batchsize)
+            rs = slice(g0 * S, g1 * S)
+            for i0 in range(0, S, iterative_samplesize):
+                res = _hip.pair_logmeanexp(plan[0], tgt_c[rs], extra if extra.shape[0] == 1 else extra[rs], plan[2], g1 - g0, S, i0,
+                                           i0 + iterative_samplesize, plan[1], b - a, add=None if add is None else add[rs], out=out[rs],
+                                           status=status)
+                if res is None:                           # the library declines this chain: every launch would
+                    return None
+        return out
+
+    def _generic_pair_logp(self, sm, targets, data_summary, batch, S, iterative_samplesize, max_iterative_batchsize, forced_emb, forced_intr,
+                           status):
+        """the same values as _kernel_pair_logp by the reference's own scheme (:2456-2700) on the ordinary kernels, for any block: per chunk of
+        (conditional inputs, samples i) the rows (g, i, j) go through the log-prob direction up to block sm and are reduced over j."""
         dims = self.target_dims_embedded if forced_emb else (self.target_dims_intrinsic if forced_intr else self.target_dims)
         first, w = sum(dims[:sm]), dims[sm]
-        nsub = len(self.layer_list)
         ba, bb = self.base_dim_indices[sm]
         tg = targets.reshape(batch, S, -1)
+        out = torch.empty((batch * S,), dtype=targets.dtype, device=targets.device)
         for g0 in range(0, batch, max_iterative_batchsize):
             g1 = min(batch, g0 + max_iterative_batchsize)
             nb = g1 - g0
             for i0 in range(0, S, iterative_samplesize):
                 ni = iterative_samplesize
+                # rows (g, i, j): x_<sm of sample j, x_sm of sample i of conditional input g; later sub-manifolds filled with ones (:2413-2416)
                 prev = tg[g0:g1, None, :, :first].expand(nb, ni, S, first)
                 fin = tg[g0:g1, i0:i0 + ni, None, first:first + w].expand(nb, ni, S, w)
                 fill = torch.ones((nb, ni, S, targets.shape[1] - first - w), dtype=targets.dtype, device=targets.device)
@@ -1809,18 +1885,11 @@ class pdf(nn.Module):
                     def rep(d):
                         return d.reshape(batch, S, -1)[g0:g1, 0].repeat_interleave(ni * S, dim=0)
                     ds2 = [rep(d) for d in data_summary] if type(data_summary) == list else rep(data_summary)
-                marks2 = []
-                base2 = self._inverse_impl(filled, None, ds2, None, forced_emb, forced_intr, False, False, status, per_block=marks2,
-                                           last_block=sm)[0]
-
-                def inc(acc, i, start):
-                    cur = 0.0 if acc[i] is None else acc[i]
-                    prev_ = start if i == 0 else acc[i - 1]
-                    return cur - (0.0 if prev_ is None else prev_)
-                if forced_emb or forced_intr:
-                    lp = _hip.normal_logp(base2[:, ba:bb]) + inc(marks2[nsub:], sm, marks2[nsub - 1]) + inc(marks2[:nsub], sm, None)
-                else:
-                    lp = _hip.normal_logp(base2[:, ba:bb]) + inc(marks2, sm, None)
+                marks = []
+                base = self._inverse_impl(filled, None, ds2, None, forced_emb, forced_intr, False, False, status, per_block=marks,
+                                          last_block=sm)[0]
+                flow, trans = _block_log_dets(marks, len(self.layer_list), forced_emb or forced_intr, False)
+                lp = _hip.normal_logp(base[:, ba:bb]) + flow[sm] + trans[sm]
                 out.reshape(batch, S)[g0:g1, i0:i0 + ni] = _hip.segment_reduce(lp, S, "logmeanexp").reshape(nb, ni)
         return out
 
@@ -1839,56 +1908,22 @@ class pdf(nn.Module):
         all_layer_forward_individual_subdims_incl_sampling produces.  `predefined_base` injects the standard-normal base samples (tests)."""
         if failsafe_crosscheck_tolerance:
             raise NotImplementedError("failsafe_crosscheck_tolerance (recheck_sampling) is outside the MI355X hot path")
-        dt, dev = self.obtain_current_dtype_n_device()
-        dev = device if device is not None else dev
-        dt = dtype if dtype is not None else dt
         S = samplesize
         assert samplesize % iterative_samplesize == 0, ("Sample size must be divisble by iterative sample size!", samplesize, iterative_samplesize)
         assert max_iterative_batchsize >= 1
-        data_summary, batch = None, 1
-        if conditional_input is not None:
-            assert self.conditional_input_dim is not None
-            if type(conditional_input) == list:
-                assert len(self.conditional_input_dim) == len(conditional_input)
-                for d, ci in zip(self.conditional_input_dim, conditional_input):
-                    assert d == ci.shape[1], "Inputs of conditional input vector do not match with pre-defined input_dims!"
-                dt, dev, batch = conditional_input[0].dtype, conditional_input[0].device, conditional_input[0].shape[0]
-                data_summary = [ci.repeat_interleave(S, dim=0) for ci in conditional_input]
-            else:
-                dt, dev, batch = conditional_input.dtype, conditional_input.device, conditional_input.shape[0]
-                data_summary = conditional_input.repeat_interleave(S, dim=0)
-        else:
-            assert self.conditional_input_dim is None, "We require conditional input, since this is a conditional PDF."
+        dt, dev, batch, data_summary = self._repeat_conditional(conditional_input, S, dtype, device)
         if not force_embedding_coordinates:
             print("#### CAUTION: Calculating entropy without forcing embedding coordinates. This might lead to undesired and wrong entropies "
                   "when using manifold PDFs!#############")
         for sm in sub_manifolds:
             assert sm == -1 or 0 <= sm < len(self.layer_list)
         nsub = len(self.layer_list)
+        forced = force_embedding_coordinates or force_intrinsic_coordinates
         out = {}
         with torch.no_grad():
-            z = predefined_base if predefined_base is not None else torch.randn((S * batch, self.total_base_dim), dtype=dt, device=dev)
-            assert z.shape == (S * batch, self.total_base_dim)
-            status = _hip.new_status(z.device) if self.check_status else None
-            marks = []
-            targets, log_det = self.all_layer_forward(z, None, data_summary, force_embedding_coordinates=force_embedding_coordinates,
-                                                      force_intrinsic_coordinates=force_intrinsic_coordinates, status=status, per_block=marks)
-            forced = force_embedding_coordinates or force_intrinsic_coordinates
-
-            def increments(acc, start):
-                res, prev = [], start
-                for m in acc:
-                    cur = 0.0 if m is None else m
-                    res.append(cur - (0.0 if prev is None else prev))
-                    prev = m
-                return res
-            flow_inc = increments(marks[:nsub], None)
-            trans_inc = increments(marks[nsub:], marks[nsub - 1]) if forced else [0.0] * nsub
-            log_pdf_dict = {"total": _hip.normal_logp(z) - log_det}
-            if return_samples or 0 in sub_manifolds:
-                for si in range(nsub if return_samples else 1):
-                    ba, bb = self.base_dim_indices[si]
-                    log_pdf_dict[si] = _hip.normal_logp(z[:, ba:bb]) - (flow_inc[si] + trans_inc[si])
+            targets, log_pdf_dict, status = self._sampling_pass(predefined_base, S * batch, dt, dev, data_summary, force_embedding_coordinates,
+                                                                force_intrinsic_coordinates,
+                                                                range(nsub) if return_samples else ([0] if 0 in sub_manifolds else []))
             xdef = back_inc = None
             for sm in sub_manifolds:
                 if verbose:
@@ -1899,16 +1934,16 @@ class pdf(nn.Module):
                     out[0] = _hip.segment_reduce(log_pdf_dict[0], S, "neg_mean")
                 else:
                     if xdef is None:                      # the targets in default coordinates, once; block k's log-det alone is its addend
+                        xdef, back = targets, []
                         if forced:
-                            back = []
                             xdef, _ = self.transform_target_space(targets, None, transform_from="embedding" if force_embedding_coordinates else "intrinsic",
                                                                   transform_to="default", per_block=back)
-                            back_inc = increments(back, None)
-                        else:
-                            xdef, back_inc = targets, [0.0] * nsub
+                        back_inc = _block_log_dets(back, nsub, forced, False)[1]
                     add = back_inc[sm] if isinstance(back_inc[sm], torch.Tensor) else None
-                    lp = self._marginal_pair_logp(sm, targets, xdef, add, data_summary, batch, S, iterative_samplesize, max_iterative_batchsize,
-                                                  force_embedding_coordinates, force_intrinsic_coordinates, status)
+                    lp = self._kernel_pair_logp(sm, xdef, add, data_summary, batch, S, iterative_samplesize, max_iterative_batchsize, status)
+                    if lp is None:
+                        lp = self._generic_pair_logp(sm, targets, data_summary, batch, S, iterative_samplesize, max_iterative_batchsize,
+                                                     force_embedding_coordinates, force_intrinsic_coordinates, status)
                     out[sm] = _hip.segment_reduce(lp, S, "neg_mean")
             self._report_status(status)
         if return_samples:
@@ -1929,21 +1964,12 @@ class pdf(nn.Module):
         `predefined_base` injects the standard-normal base samples (tests).
         Not provided: s2_entropy_scanning (needs healpy: NotImplementedError) and the reference's zlp_kent_* keys (its Kent fit is an
         optimiser of its own, outside this method).  S1 uses log c = -log(2 pi I0(kappa)) (the reference's S1 branch never assigns it)."""
-        from scipy import special
         if failsafe_crosscheck_tolerance:
             raise NotImplementedError("failsafe_crosscheck_tolerance (recheck_sampling) is outside the MI355X hot path")
         if s2_entropy_scanning:
             raise NotImplementedError("s2_entropy_scanning needs healpy and is not provided")
-        dt, dev = self.obtain_current_dtype_n_device()
-        dev = device if device is not None else dev
-        dt = dtype if dtype is not None else dt
         S = samplesize
-        batch, data_summary = 1, None
-        if conditional_input is not None:
-            first = conditional_input[0] if type(conditional_input) == list else conditional_input
-            batch, dt, dev = first.shape[0], first.dtype, first.device
-            data_summary = ([ci.repeat_interleave(S, dim=0) for ci in conditional_input] if type(conditional_input) == list
-                            else conditional_input.repeat_interleave(S, dim=0))
+        dt, dev, batch, data_summary = self._repeat_conditional(conditional_input, S, dtype, device)
         for d in self.pdf_defs_list:
             if not ("e" in d or "s" in d):
                 raise Exception("Unsupported sub pdf type for marginal moment calculation!", d)
@@ -1956,102 +1982,47 @@ class pdf(nn.Module):
                 iterative_samplesize=iterative_samplesize, max_iterative_batchsize=max_iterative_batchsize, device=dev, dtype=dt,
                 return_samples=True, verbose=verbose, predefined_base=predefined_base)
             logp = log_pdf_dict["total"]
+        kl = entropy_dict is not None
         previous_flags = self.get_embedding_flags()
         self.set_embedding_flags(True)
         try:
             with torch.no_grad():
-                if entropy_dict is None:
+                if not kl:
                     samples, _, logp, _ = self._obtain_sample(conditional_input=data_summary, predefined_target_input=predefined_base,
                                                               samplesize=S, force_embedding_coordinates=True, dtype=dt, device=dev)
                 assert samples.shape == (batch * S, self.total_target_dim_embedded)
-                host = lambda t: t.cpu().numpy()
                 rows = torch.arange(batch, device=samples.device) * S
                 for k, pdef in enumerate(self.pdf_defs_list):
                     a, b = self.target_dim_indices_embedded[k]
                     sub = samples[:, a:b]
-                    w = b - a
                     sums, cmom, amax = _hip.segment_moments(sub, S, logp)
                     arg_max = sub[rows + amax]
                     if return_samples:
-                        ret["samples_%d" % k] = host(sub.reshape(batch, S, w))
-                    cross = None
+                        ret["samples_%d" % k] = _host(sub.reshape(batch, S, b - a))
+                    # (the draws of the fit, for k = 0 only: the reverse direction below scores them)
                     if "e" in pdef:
-                        mean = sums / S
-                        var = cmom / (S - 1)
-                        approx = 0.5 * (w * (numpy.log(2 * numpy.pi) + 1) + torch.log(torch.linalg.det(var)))
-                        if entropy_dict is not None:
-                            # -mean log N(x; mean, var) = 0.5 (w log 2 pi + log det var + tr(var^-1 C) / S),  C = centred second moments
-                            tr = (torch.linalg.inv(var) * cmom).sum(dim=(1, 2)) / S
-                            cross = 0.5 * (w * numpy.log(2 * numpy.pi) + torch.log(torch.linalg.det(var)) + tr)
-                            if k == 0:
-                                draws = torch.distributions.MultivariateNormal(mean, covariance_matrix=var).sample(sample_shape=(S,))
-                                draws = draws.transpose(0, 1).reshape(batch * S, w).to(samples)
-                        varlike = var
+                        mean, varlike, approx, cross, draws = _gaussian_fit(sub, sums, cmom, S, kl, kl and k == 0)
                     else:
-                        layer0 = self.layer_list[k][0]
-                        length = (sums ** 2).sum(dim=1, keepdim=True).sqrt()
-                        mean = sums / length
-                        ang_mean, _ = layer0.eucl_to_spherical_embedding(mean, 0.0)
-                        ang, _ = layer0.eucl_to_spherical_embedding(sub, 0.0)
-                        if return_samples:
-                            ret["samples_%d_angles" % k] = host(ang.reshape(batch, S, w - 1))
-                        ret["argmax_%d_angles" % k] = host(layer0.eucl_to_spherical_embedding(arg_max, 0.0)[0])
-                        ret["mean_%d_angles" % k] = host(ang_mean)
-                        R = length / S
-                        p = w
-                        if p == 3:
-                            angs = ang.reshape(batch, S, 2)
-                            azi = angs[..., 1] - ang_mean[:, None, 1]
-                            azi = torch.where(azi < 0, azi + 2 * numpy.pi, azi)
-                            azi = torch.where(azi >= numpy.pi, azi - 2 * numpy.pi, azi)
-                            ret["azivar_%d" % k] = numpy.var(host(azi), axis=-1)
-                            ret["zenvar_%d" % k] = numpy.var(host(angs[..., 0]), axis=1)
-                        # kappa: the reference's Newton iteration on A_p(kappa) = R (batch scalars, on the host as there)
-                        Rc = host(R).astype(numpy.float64)
-                        kap = Rc * (p - Rc ** 2) / (1 - Rc ** 2)
-                        for _ in range(20):
-                            if p == 2:
-                                apk = special.i1(kap) / special.i0(kap)
-                                new = kap - (apk - Rc) / (1.0 - apk ** 2 - (1.0 / kap) * apk)
-                            else:
-                                apk = -1.0 / kap + 1.0 / numpy.tanh(kap)
-                                new = kap - (apk - Rc) / (1.0 - apk ** 2 - (2.0 / kap) * apk)
-                            diff = numpy.abs(new - kap).max()
-                            kap = new
-                            if diff < mises_abs_precision:
-                                break
-                        if p == 2:
-                            apk = special.i1(kap) / special.i0(kap)
-                            log_c = -numpy.log(2 * numpy.pi) - (numpy.log(special.i0e(kap)) + kap)
-                        else:
-                            apk = -1.0 / kap + 1.0 / numpy.tanh(kap)
-                            log_c = numpy.log(kap) - numpy.log(2 * numpy.pi) - (kap + numpy.log1p(-numpy.exp(-2 * kap)))
-                        kappa = torch.from_numpy(kap).to(mean)
-                        log_c_t = torch.from_numpy(log_c).to(mean)
-                        approx = (-log_c_t - kappa * torch.from_numpy(apk).to(mean)).squeeze(1)
-                        if entropy_dict is not None:
-                            # -mean log q = -(kappa <mean, sum x> / S + log c)
-                            cross = -((mean * sums).sum(dim=1) * kappa.squeeze(1) / S + log_c_t.squeeze(1))
-                            if k == 0:
-                                draws = torch.from_numpy(numpy.concatenate([_von_mises_fisher_draws(host(mean[g]).astype(numpy.float64), float(kap[g, 0]), S)
-                                                                            for g in range(batch)], axis=0)).to(samples)
-                        varlike = kappa
-                    ret["mean_%d" % k] = host(mean)
-                    ret["argmax_%d" % k] = host(arg_max)
-                    ret["varlike_%d" % k] = host(varlike)
-                    if entropy_dict is not None:
-                        ret["entropy_%d" % k] = host(entropy_dict[k])
-                        ret["cross_entropy_%d" % k] = host(cross)
-                        ret["kl_diff_exact_approx_%d" % k] = host(cross - entropy_dict[k])
+                        mean, varlike, approx, cross, draws, sphere = _vmf_fit(self.layer_list[k][0], sub, sums, arg_max, S, mises_abs_precision,
+                                                                               kl, kl and k == 0, return_samples)
+                        for key, v in sphere.items():
+                            ret[key % k] = v
+                    ret["mean_%d" % k] = _host(mean)
+                    ret["argmax_%d" % k] = _host(arg_max)
+                    ret["varlike_%d" % k] = _host(varlike)
+                    if kl:
+                        ret["entropy_%d" % k] = _host(entropy_dict[k])
+                        ret["cross_entropy_%d" % k] = _host(cross)
+                        ret["kl_diff_exact_approx_%d" % k] = _host(cross - entropy_dict[k])
                         if k == 0:
                             # reverse direction: draws of the fitted approximation, scored by the pdf's first sub-manifold marginal
                             rev = self._first_marginal_logp(draws, data_summary)
                             rce = _hip.segment_reduce(rev, S, "neg_mean")
-                            ret["reverse_cross_entropy_0"] = host(rce)
-                            ret["kl_diff_approx_exact_0"] = host(rce - approx)
-                    ret["approx_entropy_%d" % k] = host(approx)
-                if entropy_dict is not None:
-                    ret["entropy_total"] = host(entropy_dict["total"])
+                            ret["reverse_cross_entropy_0"] = _host(rce)
+                            ret["kl_diff_approx_exact_0"] = _host(rce - approx)
+                    ret["approx_entropy_%d" % k] = _host(approx)
+                if kl:
+                    ret["entropy_total"] = _host(entropy_dict["total"])
         finally:
             for i, f in enumerate(previous_flags):
                 self.set_embedding_flags(f, sub_pdf_index=i)
@@ -2060,14 +2031,12 @@ class pdf(nn.Module):
     def _first_marginal_logp(self, x0, data_summary):
         """log-pdf of the first sub-manifold's marginal at x0 (embedding coordinates): block 0 depends on the conditional input alone, so the
         later blocks are filled with ones and only block 0's base log-prob and log-det are kept (as the marginal entropies do)."""
-        nsub = len(self.layer_list)
         fill = torch.ones((x0.shape[0], self.total_target_dim_embedded - x0.shape[1]), dtype=x0.dtype, device=x0.device)
         marks = []
         base = self._inverse_impl(torch.cat([x0, fill], dim=1), None, data_summary, None, True, False, False, False, None, per_block=marks)[0]
         ba, bb = self.base_dim_indices[0]
-        t0 = 0.0 if marks[0] is None else marks[0]
-        f0 = (0.0 if marks[nsub] is None else marks[nsub]) - (0.0 if marks[nsub - 1] is None else marks[nsub - 1])
-        return _hip.normal_logp(base[:, ba:bb]) + f0 + t0
+        flow, trans = _block_log_dets(marks, len(self.layer_list), True, False)
+        return _hip.normal_logp(base[:, ba:bb]) + flow[0] + trans[0]
 
     # =========================================================================================== coordinate systems
     def transform_target_into_returnable_params(self, target):

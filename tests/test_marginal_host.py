@@ -77,6 +77,28 @@ def test_argument_checks():
     assert pdf.get_embedding_flags() == flags
 
 
+def test_block_log_dets_decodes_the_per_block_marks():
+    """accumulated marks (None: nothing added yet) of three blocks -> per-block increments (flow, trans), written out by hand (every value is
+    exact in binary)"""
+    from jammy_flows_amd.main.default import _block_log_dets as dec
+    zeros = [0.0, 0.0, 0.0]
+    # sampling direction: the flow marks, then (forced) the transformation marks continuing from the flows' total
+    assert dec([None, 0.5, 2.0, 2.0, 2.25, 3.0], 3, True, True) == ([0.0, 0.5, 1.5], [0.0, 0.25, 0.75])
+    assert dec([None, 0.5, 2.0], 3, False, True) == ([0.0, 0.5, 1.5], zeros)
+    # log-prob direction: (forced) the transformation marks first, the flow marks continue from their total
+    assert dec([None, 0.25, 1.0, 1.0, 1.5, 3.0], 3, True, False) == ([0.0, 0.5, 1.5], [0.0, 0.25, 0.75])
+    assert dec([None, None, None, 0.5, 0.5, -2.0], 3, True, False) == ([0.5, 0.0, -2.5], zeros)
+    assert dec([0.5, 0.5, -2.0], 3, False, False) == ([0.5, 0.0, -2.5], zeros)
+    # last_block = 1: the flow marks end after block 1
+    assert dec([None, 0.25, 1.0, 1.0, 1.5], 3, True, False) == ([0.0, 0.5], [0.0, 0.25, 0.75])
+    assert dec([None, 2.0], 3, False, False) == ([0.0, 2.0], zeros)
+    # transform_target_space alone: transformation marks and no flow
+    assert dec([None, 0.25, 1.0], 3, True, False) == ([], [0.0, 0.25, 0.75])
+    assert dec([], 3, False, False) == ([], zeros)
+    # a part nothing was added to is the python float 0.0 (entropy_iterative tells a missing addend by it)
+    assert all(type(v) is float for v in dec([None, None, None, 0.5, 0.5, -2.0], 3, True, False)[1])
+
+
 @pytest.mark.parametrize("name", ENTROPY_CASES)
 def test_fixtures_hold_what_the_gpu_tests_read(name):
     fx = fixture_io.load(name)
