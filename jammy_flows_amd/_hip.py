@@ -4,6 +4,7 @@ This is the ONLY compute path of the package: there is no CPU / eager fallback. 
 HIP kernels raises (missing library, CPU tensors, unsupported option) -- silently routing through PyTorch ops would
 void every parity claim made for the kernels.
 """
+import contextlib
 import ctypes
 import threading
 import os
@@ -431,13 +432,10 @@ def __getattr__(name):
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
-def _launch(name, tag, args, dev, unsupported_ok=False):
-    """call entry point `name` with `args` + the stream argument.  The launch goes to the TENSORS' device (`dev`, from require_device) and to
-    torch's current stream OF THAT DEVICE -- not to whatever device happens to be current: the C side sizes grids with hipGetDevice and a
-    kernel launched on device 0 with device-1 pointers faults or computes on the wrong GPU."""
-    fn = getattr(lib(), name)
-    if dev is None:
-        raise HipUnavailable("%s: no device tensor among the arguments" % name)
+def _issue(fn, name, tag, args, dev, quiet=None):
+    """the one place an entry point is called: `args` + the stream argument, on `dev` and torch's current stream of it -> return code.  The call
+    is noted in the plan this thread records (unless it failed: the caller raises), else in the active KernelTimer's records with a pair of
+    events around it (unless it returned `quiet`, the code the caller takes as "not this kernel"), else just made."""
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev)
         args = tuple(args) + (stream.cuda_stream,)
@@ -445,7 +443,7 @@ def _launch(name, tag, args, dev, unsupported_ok=False):
         if rec is not None:
             n0 = rec.num_ops()
             rc = fn(*args)
-            if rc == JF_OK:
+            if rc >= JF_OK:
                 rec.calls.append((name, tag, n0, rec.num_ops()))
         elif _TIMER is None or _MERGING:              # (a captured launch is issued by merge_end: nothing to time here)
             rc = fn(*args)
@@ -455,8 +453,19 @@ def _launch(name, tag, args, dev, unsupported_ok=False):
             e0.record(stream)
             rc = fn(*args)
             e1.record(stream)
-            if not (unsupported_ok and rc == JF_ERR_UNSUPPORTED):
+            if rc != quiet:
                 _TIMER.records.append((name, tag, e0, e1))
+    return rc
+
+
+def _launch(name, tag, args, dev, unsupported_ok=False):
+    """call entry point `name` with `args` + the stream argument.  The launch goes to the TENSORS' device (`dev`, from require_device) and to
+    torch's current stream OF THAT DEVICE -- not to whatever device happens to be current: the C side sizes grids with hipGetDevice and a
+    kernel launched on device 0 with device-1 pointers faults or computes on the wrong GPU."""
+    fn = getattr(lib(), name)
+    if dev is None:
+        raise HipUnavailable("%s: no device tensor among the arguments" % name)
+    rc = _issue(fn, name, tag, args, dev, JF_ERR_UNSUPPORTED if unsupported_ok else None)
     if unsupported_ok and rc == JF_ERR_UNSUPPORTED:
         return False                                  # the caller has another kernel path for this configuration
     _check(rc, name)
@@ -479,6 +488,134 @@ def _rowmajor(t):
     if t.shape[0] > 1 and t.stride(0) == 0:      # expanded rows (stride 0): kernels that derive row counts from the stride divide by it
         t = t.contiguous()
     return t
+
+
+# ---- the argument conventions of the C ABI (include/jammy_hip.h), each stated once.  Every tensor a helper makes (_rowmajor / .contiguous()) comes
+# back to the wrapper, which holds it until its _launch has returned: the pointers in an argument tuple keep nothing alive.
+def _param_rows(params, B, dtype=None, what=None):
+    """parameter rows of a chain: None or zero width = the chain takes no parameters (NULL), else (1 | B, P) rows, unit stride inside a row;
+    param_batch = 1 for a single row that every input row shares, else B -> (row-major params or None, pointer, row stride, param_batch).
+    dtype: checked against the rows' when given.  what: names the wrapper in the row-count error; None = the count is not checked (the backward
+    wrappers, which see what their forward call has checked)."""
+    if params is None or (params.dim() == 2 and params.shape[1] == 0):
+        return None, None, 0, 1
+    params = _rowmajor(params)
+    if dtype is not None and params.dtype != dtype:
+        raise TypeError("parameter dtype %s != input dtype %s" % (params.dtype, dtype))
+    if what is not None and params.shape[0] not in (1, B):
+        raise ValueError("%s: extra_inputs must have 1 or B=%d rows, got %d" % (what, B, params.shape[0]))
+    return params, _ptr(params), params.stride(0), 1 if params.shape[0] == 1 else B
+
+
+def _flow_io(x, D, log_det, x_out, want_base_logp, check_log_det=False):
+    """what a flow launch takes and writes besides its input rows `x` -> (log_det contiguous or None, x_out (B, D) unless given, log_det_out (B,),
+    base_logp_out (B,) or None)"""
+    B = x.shape[0]
+    if log_det is not None:
+        log_det = log_det.contiguous()
+        if check_log_det and (log_det.dtype != x.dtype or log_det.shape[0] != B):
+            raise ValueError("log_det must be a (B,) tensor of the input dtype")
+    if x_out is None:
+        x_out = torch.empty((B, D), dtype=x.dtype, device=x.device)
+    ld_out = torch.empty((B,), dtype=x.dtype, device=x.device)
+    blp_out = torch.empty((B,), dtype=x.dtype, device=x.device) if want_base_logp else None
+    return log_det, x_out, ld_out, blp_out
+
+
+def _flow_result(x_out, ld_out, blp_out, want_base_logp):
+    return (x_out, ld_out, blp_out) if want_base_logp else (x_out, ld_out)
+
+
+def _cotangents(g_xout, g_ld, g_blp):
+    """upstream gradients of (x_out, log_det_out, base_logp_out), any of them None = zero -> (the tensors as passed: g_xout row-major, the other
+    two contiguous; the four arguments they make: g_xout, its row stride or 0, g_ld, g_blp)"""
+    g_xout = None if g_xout is None else _rowmajor(g_xout)
+    g_ld = None if g_ld is None else g_ld.contiguous()
+    g_blp = None if g_blp is None else g_blp.contiguous()
+    return (g_xout, g_ld, g_blp), (_ptr(g_xout), 0 if g_xout is None else g_xout.stride(0), _ptr(g_ld), _ptr(g_blp))
+
+
+def _row_list(tensors, B, dtype, what, copies=None):
+    """jf_row_list of (B,) tensors.  The entries must be contiguous and of `dtype` -- or, with a list `copies`, are made contiguous and appended
+    to it unchecked: the caller holds that list until its launch is issued (combine_rows: ADVICE r04)."""
+    r = jf_row_list()
+    r.n = len(tensors)
+    for i, t in enumerate(tensors):
+        if copies is not None:
+            t = t.contiguous()
+            copies.append(t)
+        elif t.dtype != dtype or t.shape != (B,) or not t.is_contiguous():
+            raise ValueError("%s: pre_ld / pre_blp entries are contiguous (B,) tensors of dtype %s" % (what, dtype))
+        r.p[i] = _ptr(t)
+    return r
+
+
+def _pre_sums(pre_ld, pre_blp, x, what):
+    """the earlier blocks' log-dets / base log-probs a last block adds in front of its own -> (row list, row list, total (B,) to be written)"""
+    pre_ld, pre_blp = list(pre_ld or []), list(pre_blp or [])
+    require_device(x, *(pre_ld + pre_blp))
+    B = x.shape[0]
+    return _row_list(pre_ld, B, x.dtype, what), _row_list(pre_blp, B, x.dtype, what), torch.empty((B,), dtype=x.dtype, device=x.device)
+
+
+def _mlp_head(inp, w1, b1, what=None, dtype=None, in_place=None):
+    """first layer of a Linear-tanh-Linear head: inp (B, K1) and w1 (H, K1) row-major, b1 (H,) contiguous -> ((inp, w1, b1, seg), the five leading
+    arguments inp, stride, w1, stride, b1, B, K1, H).  what: names the wrapper in the shape error; None = shapes are not checked (the backward
+    wrappers).  dtype: checked against the three tensors' when given.
+    A SegInput is materialised -- unless `in_place` names its dtype and it is worth reading in place: then seg is the SegInput, inp its first
+    segment (for the device / dtype checks) and the segment array + count take the place of inp, stride."""
+    seg = None
+    if isinstance(inp, SegInput):
+        if in_place is not None and inp.in_place_ok and inp.dtype == in_place:
+            seg = inp
+            inp = seg.segments[0][0]
+        else:
+            inp = inp.materialize()
+    inp, w1, b1 = _rowmajor(inp), _rowmajor(w1), b1.contiguous()
+    B, K1 = seg.shape if seg else inp.shape
+    H = w1.shape[0]
+    if what is not None and (w1.shape[1] != K1 or b1.shape[0] != H):
+        raise ValueError("%s: inconsistent shapes" % what)
+    if dtype is not None and any(t.dtype != dtype for t in (inp, w1, b1)):
+        raise TypeError("%s: %s inputs expected" % (what, dtype))
+    first = (seg.c_array(), len(seg.segments)) if seg else (_ptr(inp), inp.stride(0))
+    return (inp, w1, b1, seg), first + (_ptr(w1), w1.stride(0), _ptr(b1)), B, K1, H
+
+
+def _mlp_second(w2, b2, H, what, dtype):
+    """second layer of a Linear-tanh-Linear head: w2 (N, H) row-major, b2 (N,) contiguous, both of `dtype` -> ((w2, b2), the three arguments w2,
+    stride, b2, N)"""
+    w2, b2 = _rowmajor(w2), b2.contiguous()
+    if w2.shape[1] != H or b2.shape[0] != w2.shape[0]:
+        raise ValueError("%s: inconsistent shapes" % what)
+    if w2.dtype != dtype or b2.dtype != dtype:
+        raise TypeError("%s: dtype mismatch" % what)
+    return (w2, b2), (_ptr(w2), w2.stride(0), _ptr(b2)), w2.shape[0]
+
+
+def _amlp_weights(v1, u1, b1, v2, u2, b2):
+    """the low-rank weight set of a two-stage AmortizableMLP: W1 = u1 v1 (v1 None: the full first stage u1 (H, K1)), W2 = u2 v2, all contiguous
+    -> ((v1 or None, u1, b1, v2, u2, b2), their six pointers, r1 (0 without v1), r2, H)"""
+    ws = (None if v1 is None else v1.contiguous(),) + tuple(t.contiguous() for t in (u1, b1, v2, u2, b2))
+    return ws, tuple(_ptr(t) for t in ws), 0 if v1 is None else v1.shape[0], v2.shape[0], v2.shape[1]
+
+
+def _segments(segments, B, dtype, what):
+    """(tensor (B, n), kind) segments of a conditioning row block -> (the same with row-major tensors, width of the block they make)"""
+    segments = [(_rowmajor(t), kind) for t, kind in segments]
+    for i, (t, kind) in enumerate(segments):
+        if t.dtype != dtype or t.shape[0] != B:
+            raise TypeError("%s: segment %d has dtype %s / %d rows, expected %s / %d" % (what, i, t.dtype, t.shape[0], dtype, B))
+        if kind != 0 and t.shape[1] != kind:
+            raise ValueError("%s: an S%d segment needs %d intrinsic columns" % (what, kind, kind))
+    return segments, sum(t.shape[1] if kind == 0 else kind + 1 for t, kind in segments)
+
+
+def _segment_array(segments):
+    arr = (jf_cond_segment * len(segments))()
+    for i, (t, kind) in enumerate(segments):
+        arr[i] = jf_cond_segment(_ptr(t), t.stride(0), kind, t.shape[1])
+    return arr
 
 
 def new_status(device):
@@ -506,6 +643,9 @@ def mapped_status(device):
 
 
 # --------------------------------------------------------------------------------------------------------------
+_SAME_DEVICE = contextlib.nullcontext()
+
+
 class StepPlan:
     """a recorded step (include/jammy_hip.h "step plans", csrc/plan.hip): every launch the entry points make between begin() and end() is
     stored instead of issued; launch(bases) re-issues all of them from C in one call, with the device pointers into the declared slots
@@ -590,11 +730,8 @@ class StepPlan:
             self._replays_under_timer = getattr(self, "_replays_under_timer", 0) + 1
             if self not in _TIMER.plans:
                 _TIMER.plans.append(self)
-        if torch.cuda.current_device() == dev.index:
+        with (_SAME_DEVICE if torch.cuda.current_device() == dev.index else torch.cuda.device(dev)):   # (a replay on the current device switches nothing)
             rc = lib().jf_plan_launch(self.handle, b, self.n_slots, (stream if stream is not None else torch.cuda.current_stream(dev)).cuda_stream)
-        else:
-            with torch.cuda.device(dev):
-                rc = lib().jf_plan_launch(self.handle, b, self.n_slots, (stream if stream is not None else torch.cuda.current_stream(dev)).cuda_stream)
         _check(rc, "jf_plan_launch")
 
     def read_timing(self):
@@ -619,14 +756,9 @@ def combine_rows(ld_list, blp_list, want_total=True):
     B = like.shape[0]
     keep = []                                          # contiguous copies stay alive until their launch is issued
 
-    def lst(items):
-        r = jf_row_list()
-        r.n = len(items)
-        for i, t in enumerate(items):
-            c = t.contiguous()
-            keep.append(c)
-            r.p[i] = _ptr(c)
-        return r
+    def launch(ld_items, blp_items, *outs):
+        a, b = (_row_list(items, B, like.dtype, "combine_rows", copies=keep) for items in (ld_items, blp_items))
+        _launch("jf_combine_rows" + _suffix(like), "", (ctypes.byref(a), ctypes.byref(b), B) + tuple(_ptr(o) for o in outs), dev)
 
     def fold(items):
         """more than JF_MAX_ROW_LISTS entries: partial sums in list order, each fed back as entry 0 of the next launch (same summation order)"""
@@ -634,8 +766,7 @@ def combine_rows(ld_list, blp_list, want_total=True):
         while len(items) > JF_MAX_ROW_LISTS:
             head, items = items[:JF_MAX_ROW_LISTS], items[JF_MAX_ROW_LISTS:]
             part = torch.empty_like(like)
-            a, b = lst(head), lst([])
-            _launch("jf_combine_rows" + _suffix(like), "", (ctypes.byref(a), ctypes.byref(b), B, _ptr(part), None, None), dev)
+            launch(head, [], part, None, None)
             items = [part] + items
         return items
     ld_list, blp_list = fold(ld_list), fold(blp_list)
@@ -643,8 +774,7 @@ def combine_rows(ld_list, blp_list, want_total=True):
     blp_out = torch.empty_like(like) if len(blp_list) > 1 else None
     total = torch.empty_like(like) if (want_total and ld_list and blp_list) else None
     if ld_out is not None or blp_out is not None or total is not None:
-        a, b = lst(ld_list), lst(blp_list)
-        _launch("jf_combine_rows" + _suffix(like), "", (ctypes.byref(a), ctypes.byref(b), B, _ptr(ld_out), _ptr(blp_out), _ptr(total)), dev)
+        launch(ld_list, blp_list, ld_out, blp_out, total)
     return (ld_out if ld_out is not None else (ld_list[0] if ld_list else None),
             blp_out if blp_out is not None else (blp_list[0] if blp_list else None), total)
 
@@ -674,23 +804,7 @@ def merge_end(like):
     global _MERGING
     dev = require_device(like)
     _MERGING = False
-    fn = lib().jf_merge_end
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev)
-        rec = _recording()
-        if rec is not None:
-            n0 = rec.num_ops()
-            rc = int(fn(stream.cuda_stream))
-            rec.calls.append(("jf_merge_end", "", n0, rec.num_ops()))
-        elif _TIMER is None:
-            rc = int(fn(stream.cuda_stream))
-        else:
-            e0 = torch.cuda.Event(enable_timing=True)
-            e1 = torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
-            rc = int(fn(stream.cuda_stream))
-            e1.record(stream)
-            _TIMER.records.append(("jf_merge_end", "", e0, e1))
+    rc = _issue(lib().jf_merge_end, "jf_merge_end", "", (), dev)          # (declined or not, the blocks' launches are issued inside this call)
     if rc != JF_MERGE_DECLINED:
         _check(rc, "jf_merge_end")
     return rc == JF_OK
@@ -712,6 +826,11 @@ def gf_layer_array(structs):
     return arr
 
 
+def mchain_layer_array(fam, structs):
+    """the layer structs of a manifold chain of family `fam` as the array its entry points take"""
+    return (MCHAIN_LAYER_TYPES[fam] * len(structs))(*structs)
+
+
 # When set to a list, every spline-carrying chain launch appends its (B, n_searches) int64 tensor of raw searchsorted results
 # (execution order, -3 = not written, -2 = row skipped by an identity region): the integer output of the bit-exact parity tests.
 BINS_LOG = None
@@ -729,56 +848,36 @@ def gf_chain(direction, x, log_det, params, layer_array, n_layers, D, x_out=None
     want_total (with want_base_logp, 'inv'): the launch also writes total = base_logp + log_det (jf_gf_chain_inv_total)."""
     dev = require_device(x, log_det, params, x_out, base_logp_in, status)
     x = _rowmajor(x)
-    params = _rowmajor(params)
-    if params.dtype != x.dtype:
-        raise TypeError("parameter dtype %s != input dtype %s" % (params.dtype, x.dtype))
     B = x.shape[0]
+    params, pptr, pstride, pb = _param_rows(params, B, x.dtype, "gf_chain")
     if x.shape[1] != D:
         raise ValueError("expected %d target columns, got %d" % (D, x.shape[1]))
-    if params.shape[0] not in (1, B):
-        raise ValueError("extra_inputs must have 1 or B=%d rows, got %d" % (B, params.shape[0]))
-    if log_det is not None:
-        log_det = log_det.contiguous()
-        if log_det.dtype != x.dtype or log_det.shape[0] != B:
-            raise ValueError("log_det must be a (B,) tensor of the input dtype")
-    if x_out is None:
-        x_out = torch.empty((B, D), dtype=x.dtype, device=x.device)
-    ld_out = torch.empty((B,), dtype=x.dtype, device=x.device)
+    log_det, x_out, ld_out, blp_out = _flow_io(x, D, log_det, x_out, want_base_logp and direction == "inv", check_log_det=True)
     suf = _suffix(x)
-    pb = 1 if (params.shape[0] == 1 and B != 1) else params.shape[0]
-    if B == 1:
-        pb = 1
     bins = None
     if BINS_LOG is not None:
         n_spl = sum(1 for i in range(n_layers) if layer_array[i].nonlinear_stretch_type == GF_STRETCH_RQ_SPLINES)
         if n_spl:
             bins = torch.full((B, n_spl * D), -3, dtype=torch.int64, device=x.device)
             BINS_LOG.append(bins)
-    bs = bins.stride(0) if bins is not None else 0
+    tag = "bcast" if pb == 1 else "per-sample"
+    # every g chain entry point: these arguments, [base_logp_in, base_logp_out[, total]] ('inv'), the bins, the status words[, the table]
+    args = (_ptr(x), x.stride(0), _ptr(log_det), pptr, pstride, pb, B, D, n_layers, layer_array, _ptr(x_out), x_out.stride(0), _ptr(ld_out))
+    tail = (_ptr(bins), bins.stride(0) if bins is not None else 0, _ptr(status))
     if direction == "inv" and want_total and want_base_logp:
-        blp_out = torch.empty((B,), dtype=x.dtype, device=x.device)
         total = torch.empty((B,), dtype=x.dtype, device=x.device)
-        _launch("jf_gf_chain_inv_total" + suf, "bcast" if pb == 1 else "per-sample",
-                (_ptr(x), x.stride(0), _ptr(log_det), _ptr(params), params.stride(0), pb, B, D, n_layers, layer_array, _ptr(x_out),
-                 x_out.stride(0), _ptr(ld_out), _ptr(base_logp_in), _ptr(blp_out), _ptr(total), _ptr(bins), bs, _ptr(status)), dev)
+        _launch("jf_gf_chain_inv_total" + suf, tag, args + (_ptr(base_logp_in), _ptr(blp_out), _ptr(total)) + tail, dev)
         return x_out, ld_out, blp_out, total
     if direction == "inv":
-        blp_out = torch.empty((B,), dtype=x.dtype, device=x.device) if want_base_logp else None
-        _launch("jf_gf_chain_inv" + suf, "bcast" if pb == 1 else "per-sample",
-                (_ptr(x), x.stride(0), _ptr(log_det), _ptr(params), params.stride(0), pb, B, D, n_layers, layer_array, _ptr(x_out),
-                 x_out.stride(0), _ptr(ld_out), _ptr(base_logp_in), _ptr(blp_out), _ptr(bins), bs, _ptr(status)), dev)
-        return (x_out, ld_out, blp_out) if want_base_logp else (x_out, ld_out)
+        _launch("jf_gf_chain_inv" + suf, tag, args + (_ptr(base_logp_in), _ptr(blp_out)) + tail, dev)
+        return _flow_result(x_out, ld_out, blp_out, want_base_logp)
     if pb == 1 and B >= FWD_TABLE_MIN_ROWS:
         # row-independent parameters: every (layer, coordinate) inverts one fixed function for all rows -- the library tabulates it first and
         # the solves start from the interpolated value (jf_gf_chain_fwd_tab); the table is a temporary of this call
         table = torch.empty((int(lib().jf_gf_chain_fwd_table_elems(D, n_layers)),), dtype=x.dtype, device=x.device)
-        _launch("jf_gf_chain_fwd_tab" + suf, "bcast",
-                (_ptr(x), x.stride(0), _ptr(log_det), _ptr(params), params.stride(0), pb, B, D, n_layers, layer_array, _ptr(x_out), x_out.stride(0),
-                 _ptr(ld_out), _ptr(bins), bs, _ptr(status), _ptr(table)), dev)
+        _launch("jf_gf_chain_fwd_tab" + suf, "bcast", args + tail + (_ptr(table),), dev)
         return x_out, ld_out
-    _launch("jf_gf_chain_fwd" + suf, "bcast" if pb == 1 else "per-sample",
-            (_ptr(x), x.stride(0), _ptr(log_det), _ptr(params), params.stride(0), pb, B, D, n_layers, layer_array, _ptr(x_out), x_out.stride(0),
-             _ptr(ld_out), _ptr(bins), bs, _ptr(status)), dev)
+    _launch("jf_gf_chain_fwd" + suf, tag, args + tail, dev)
     return x_out, ld_out
 
 
@@ -786,18 +885,19 @@ def gf_chain_inv_cot(x, params, layer_array, n_layers, D, cot):
     """J^{-T} cot for the Jacobian J of gf_chain('inv', x, ...) at x (the co-vector carried through the layers: jf_gf_chain_inv_cot); None for layers
     with the general options (the caller then solves with a dense Jacobian)"""
     dev = require_device(x, params, cot)
-    x, params, cot = _rowmajor(x), _rowmajor(params), _rowmajor(cot)
+    x, cot = _rowmajor(x), _rowmajor(cot)
     B = x.shape[0]
-    if params.dtype != x.dtype or cot.dtype != x.dtype or cot.shape != (B, D) or x.shape != (B, D) or params.shape[0] not in (1, B):
+    if params.dtype != x.dtype or cot.dtype != x.dtype or cot.shape != (B, D) or x.shape != (B, D):     # (a dtype mismatch is a ValueError here)
         raise ValueError("gf_chain_inv_cot: inconsistent shapes / dtypes")
+    params, pptr, pstride, pb = _param_rows(params, B, None, "gf_chain_inv_cot")
     out = torch.empty((B, D), dtype=x.dtype, device=x.device)
     if B == 0:
         return out
     x_out = torch.empty((B, D), dtype=x.dtype, device=x.device)
     ld_out = torch.empty((B,), dtype=x.dtype, device=x.device)
-    ok = _launch("jf_gf_chain_inv_cot" + _suffix(x), "bcast" if params.shape[0] == 1 else "per-sample",
-                 (_ptr(x), x.stride(0), _ptr(params), params.stride(0), 1 if params.shape[0] == 1 else B, B, D, n_layers, layer_array, _ptr(cot),
-                  cot.stride(0), _ptr(out), out.stride(0), _ptr(x_out), x_out.stride(0), _ptr(ld_out)), dev, unsupported_ok=True)
+    ok = _launch("jf_gf_chain_inv_cot" + _suffix(x), "bcast" if pb == 1 else "per-sample",
+                 (_ptr(x), x.stride(0), pptr, pstride, pb, B, D, n_layers, layer_array, _ptr(cot), cot.stride(0), _ptr(out), out.stride(0),
+                  _ptr(x_out), x_out.stride(0), _ptr(ld_out)), dev, unsupported_ok=True)
     return out if ok is not False else None
 
 
@@ -805,26 +905,20 @@ def gf_chain_inv_bwd(x, params, layer_array, n_layers, D, g_xout, g_ld, g_blp, s
     """vector-Jacobian product of gf_chain('inv', ...): upstream gradients of (x_out, log_det_out, base_logp_out) -> (g_x (B, D), g_params).
     g_params has the shape of `params`: (B, P) per-sample, (1, P) for permanent parameters (partial sums of the launch added up here)."""
     dev = require_device(x, params, g_xout, g_ld, g_blp, status)
-    x, params = _rowmajor(x), _rowmajor(params)
-    B = x.shape[0]
-    pb = 1 if (params.shape[0] == 1) else B
-    if params.shape[0] not in (1, B):
-        raise ValueError("params must have 1 or B rows")
-    if g_xout is not None:
-        g_xout = _rowmajor(g_xout)
-    g_ld = None if g_ld is None else g_ld.contiguous()
-    g_blp = None if g_blp is None else g_blp.contiguous()
+    x = _rowmajor(x)
+    B, P = x.shape[0], params.shape[1]
+    params, pptr, pstride, pb = _param_rows(params, B, None, "gf_chain_inv_bwd")
+    held, g_args = _cotangents(g_xout, g_ld, g_blp)
     g_x = torch.empty((B, D), dtype=x.dtype, device=x.device)
-    P = params.shape[1]
     if pb == 1:
+        # permanent parameters: the launch leaves partial sums (one slab per workgroup), added up below in a fixed order
         n_part = int(lib().jf_gf_chain_inv_bwd_partials(B, D))
         g_p = (torch.zeros if B == 0 else torch.empty)((n_part, P), dtype=x.dtype, device=x.device)     # (no rows: no launch writes the partials)
     else:
         g_p = torch.empty((B, P), dtype=x.dtype, device=x.device)
     _launch("jf_gf_chain_inv_bwd" + _suffix(x), "bcast" if pb == 1 else "per-sample",
-            (_ptr(x), x.stride(0), _ptr(params), params.stride(0), pb, B, D, n_layers, layer_array, _ptr(g_xout),
-             g_xout.stride(0) if g_xout is not None else 0, _ptr(g_ld), _ptr(g_blp), _ptr(g_x), g_x.stride(0), _ptr(g_p), g_p.stride(0),
-             _ptr(status)), dev)
+            (_ptr(x), x.stride(0), pptr, pstride, pb, B, D, n_layers, layer_array) + g_args
+            + (_ptr(g_x), g_x.stride(0), _ptr(g_p), g_p.stride(0), _ptr(status)), dev)
     if pb == 1:
         g_p = slab_sum(g_p)[0].unsqueeze(0)
     return g_x, g_p
@@ -849,24 +943,16 @@ def gf_chain_fits(layer_array, n_layers, D, dtype, bcast, backward=False, on_chi
 def cond_gf_chain_inv(inp, w1, b1, w2, b2, x, log_det, layer_array, n_layers, D, x_out=None, base_logp_in=None, want_base_logp=False, status=None):
     """amortisation MLP (Linear-tanh-Linear) + the chain of g layers it parametrises in ONE launch; the parameter block stays on chip."""
     dev = require_device(inp, w1, b1, w2, b2, x, log_det, x_out, base_logp_in, status)
-    inp, w1, w2, x = _rowmajor(inp), _rowmajor(w1), _rowmajor(w2), _rowmajor(x)
-    B, K1 = inp.shape
-    H = w1.shape[0]
-    if x.shape[0] != B or x.shape[1] != D or w1.shape[1] != K1 or w2.shape[1] != H or b1.shape[0] != H or b2.shape[0] != w2.shape[0]:
+    x = _rowmajor(x)
+    held, head, B, K1, H = _mlp_head(inp, w1, b1, "cond_gf_chain_inv", x.dtype)
+    held2, second, N = _mlp_second(w2, b2, H, "cond_gf_chain_inv", x.dtype)
+    if x.shape[0] != B or x.shape[1] != D:
         raise ValueError("cond_gf_chain_inv: inconsistent shapes")
-    if any(t.dtype != x.dtype for t in (inp, w1, b1, w2, b2)):
-        raise TypeError("cond_gf_chain_inv: dtype mismatch")
-    if log_det is not None:
-        log_det = log_det.contiguous()
-    if x_out is None:
-        x_out = torch.empty((B, D), dtype=x.dtype, device=x.device)
-    ld_out = torch.empty((B,), dtype=x.dtype, device=x.device)
-    blp_out = torch.empty((B,), dtype=x.dtype, device=x.device) if want_base_logp else None
-    _launch("jf_cond_gf_chain_inv" + _suffix(x), "K%d_H%d_N%d_D%d" % (K1, H, w2.shape[0], D),
-            (_ptr(inp), inp.stride(0), _ptr(w1), w1.stride(0), _ptr(b1.contiguous()), _ptr(w2), w2.stride(0), _ptr(b2.contiguous()), K1, H,
-             _ptr(x), x.stride(0), _ptr(log_det), B, D, n_layers, layer_array, _ptr(x_out), x_out.stride(0), _ptr(ld_out), _ptr(base_logp_in),
-             _ptr(blp_out), _ptr(status)), dev)
-    return (x_out, ld_out, blp_out) if want_base_logp else (x_out, ld_out)
+    log_det, x_out, ld_out, blp_out = _flow_io(x, D, log_det, x_out, want_base_logp)
+    _launch("jf_cond_gf_chain_inv" + _suffix(x), "K%d_H%d_N%d_D%d" % (K1, H, N, D),
+            head + second + (K1, H, _ptr(x), x.stride(0), _ptr(log_det), B, D, n_layers, layer_array, _ptr(x_out), x_out.stride(0), _ptr(ld_out),
+                             _ptr(base_logp_in), _ptr(blp_out), _ptr(status)), dev)
+    return _flow_result(x_out, ld_out, blp_out, want_base_logp)
 
 
 def amlp_gf_chain_inv(inp, v1, u1, b1, v2, u2, b2, x, log_det, layer_array, n_layers, D, x_out=None, base_logp_in=None, want_base_logp=False,
@@ -876,23 +962,14 @@ def amlp_gf_chain_inv(inp, v1, u1, b1, v2, u2, b2, x, log_det, layer_array, n_la
     dev = require_device(inp, v1, u1, b1, v2, u2, b2, x, log_det, x_out, base_logp_in, status)
     inp, x = _rowmajor(inp), _rowmajor(x)
     B, K1 = inp.shape
-    H, r2 = v2.shape[1], v2.shape[0]
-    r1 = 0 if v1 is None else v1.shape[0]
-    ws = [t.contiguous() for t in (u1, b1, v2, u2, b2)]
-    v1c = None if v1 is None else v1.contiguous()
-    if any(t.dtype != x.dtype for t in ws + [inp]) or x.shape != (B, D) or u2.shape[1] != r2 or b2.shape[0] != u2.shape[0]:
+    ws, w_args, r1, r2, H = _amlp_weights(v1, u1, b1, v2, u2, b2)
+    if any(t.dtype != x.dtype for t in ws[1:] + (inp,)) or x.shape != (B, D) or u2.shape[1] != r2 or b2.shape[0] != u2.shape[0]:
         raise ValueError("amlp_gf_chain_inv: inconsistent shapes / dtypes")
-    if log_det is not None:
-        log_det = log_det.contiguous()
-    if x_out is None:
-        x_out = torch.empty((B, D), dtype=x.dtype, device=x.device)
-    ld_out = torch.empty((B,), dtype=x.dtype, device=x.device)
-    blp_out = torch.empty((B,), dtype=x.dtype, device=x.device) if want_base_logp else None
+    log_det, x_out, ld_out, blp_out = _flow_io(x, D, log_det, x_out, want_base_logp)
     _launch("jf_amlp_gf_chain_inv" + _suffix(x), "K%d_H%d_N%d_D%d_r%d" % (K1, H, u2.shape[0], D, r2),
-            (_ptr(inp), inp.stride(0), _ptr(v1c), _ptr(ws[0]), _ptr(ws[1]), _ptr(ws[2]), _ptr(ws[3]), _ptr(ws[4]), K1, H, r1, r2, _ptr(x), x.stride(0),
-             _ptr(log_det), B, D, n_layers, layer_array, _ptr(x_out), x_out.stride(0), _ptr(ld_out), _ptr(base_logp_in), _ptr(blp_out), _ptr(status)),
-            dev)
-    return (x_out, ld_out, blp_out) if want_base_logp else (x_out, ld_out)
+            (_ptr(inp), inp.stride(0)) + w_args + (K1, H, r1, r2, _ptr(x), x.stride(0), _ptr(log_det), B, D, n_layers, layer_array, _ptr(x_out),
+                                                   x_out.stride(0), _ptr(ld_out), _ptr(base_logp_in), _ptr(blp_out), _ptr(status)), dev)
+    return _flow_result(x_out, ld_out, blp_out, want_base_logp)
 
 
 LOWRANK_GF_MAX_RANK = 8
@@ -948,11 +1025,7 @@ def lowrank_gf_chain_inv(t2, u2, b2, x, log_det, layer_array, n_layers, D, base_
     B, r2 = t2.shape
     if x.dtype != torch.float64 or any(t.dtype != torch.float64 for t in (t2, u2, b2)) or x.shape != (B, D) or u2.shape[1] != r2 or b2.shape[0] != u2.shape[0]:
         raise ValueError("lowrank_gf_chain_inv: inconsistent shapes / dtypes")
-    if log_det is not None:
-        log_det = log_det.contiguous()
-    x_out = torch.empty((B, D), dtype=x.dtype, device=x.device)
-    ld_out = torch.empty((B,), dtype=x.dtype, device=x.device)
-    blp_out = torch.empty((B,), dtype=x.dtype, device=x.device) if want_base_logp else None
+    log_det, x_out, ld_out, blp_out = _flow_io(x, D, log_det, None, want_base_logp)
     aux = torch.empty((n_layers, LOWRANK_GF_AUX, 2, B, 4), dtype=x.dtype, device=x.device) if want_aux else None
     ok = _launch("jf_lowrank_gf_chain_inv_f64", "N%d_D%d_r%d" % (u2.shape[0], D, r2),
                  (_ptr(t2), t2.stride(0), _ptr(u2), _ptr(b2), r2, _ptr(x), x.stride(0), _ptr(log_det), B, D, n_layers, layer_array, _ptr(x_out),
@@ -969,9 +1042,7 @@ def lowrank_gf_chain_inv_bwd(t2, u2, b2, aux, x_out, layer_array, n_layers, D, g
     u2, b2 = u2.contiguous(), b2.contiguous()
     B, r2 = t2.shape
     N = u2.shape[0]
-    g_xout = None if g_xout is None else _rowmajor(g_xout)
-    g_ld = None if g_ld is None else g_ld.contiguous()
-    g_blp = None if g_blp is None else g_blp.contiguous()
+    held, g_args = _cotangents(g_xout, g_ld, g_blp)
     g_x = torch.empty((B, D), dtype=t2.dtype, device=t2.device)
     g_t2 = torch.empty((B, LOWRANK_GF_MAX_RANK), dtype=t2.dtype, device=t2.device)
     g_u2 = torch.empty((N, r2), dtype=t2.dtype, device=t2.device)
@@ -980,9 +1051,8 @@ def lowrank_gf_chain_inv_bwd(t2, u2, b2, aux, x_out, layer_array, n_layers, D, g
         return g_x, g_t2[:, :r2], g_u2.zero_(), g_b2.zero_()
     work = torch.empty((int(lib().jf_lowrank_gf_workspace_doubles(B, n_layers)),), dtype=t2.dtype, device=t2.device)
     _launch("jf_lowrank_gf_chain_inv_bwd_f64", "N%d_D%d_r%d" % (N, D, r2),
-            (_ptr(t2), t2.stride(0), _ptr(u2), _ptr(b2), r2, _ptr(aux), _ptr(x_out), x_out.stride(0), B, D, n_layers, layer_array, _ptr(g_xout),
-             0 if g_xout is None else g_xout.stride(0), _ptr(g_ld), _ptr(g_blp), _ptr(g_x), g_x.stride(0), _ptr(g_t2), _ptr(g_u2), _ptr(g_b2),
-             _ptr(work), _ptr(status)), dev)
+            (_ptr(t2), t2.stride(0), _ptr(u2), _ptr(b2), r2, _ptr(aux), _ptr(x_out), x_out.stride(0), B, D, n_layers, layer_array) + g_args
+            + (_ptr(g_x), g_x.stride(0), _ptr(g_t2), _ptr(g_u2), _ptr(g_b2), _ptr(work), _ptr(status)), dev)
     return g_x, g_t2[:, :r2], g_u2, g_b2
 
 
@@ -994,20 +1064,13 @@ def amlp_gf_chain_fwd(inp, v1, u1, b1, v2, u2, b2, z, log_det, layer_array, n_la
         return None
     inp, z = _rowmajor(inp), _rowmajor(z)
     B, K1 = inp.shape
-    H, r2 = v2.shape[1], v2.shape[0]
-    r1 = 0 if v1 is None else v1.shape[0]
-    ws = [t.contiguous() for t in (u1, b1, v2, u2, b2)]
-    v1c = None if v1 is None else v1.contiguous()
-    if any(t.dtype != z.dtype for t in ws + [inp]) or z.shape != (B, D) or u2.shape[1] != r2 or b2.shape[0] != u2.shape[0]:
+    ws, w_args, r1, r2, H = _amlp_weights(v1, u1, b1, v2, u2, b2)
+    if any(t.dtype != z.dtype for t in ws[1:] + (inp,)) or z.shape != (B, D) or u2.shape[1] != r2 or b2.shape[0] != u2.shape[0]:
         raise ValueError("amlp_gf_chain_fwd: inconsistent shapes / dtypes")
-    if log_det is not None:
-        log_det = log_det.contiguous()
-    if x_out is None:
-        x_out = torch.empty((B, D), dtype=z.dtype, device=z.device)
-    ld_out = torch.empty((B,), dtype=z.dtype, device=z.device)
+    log_det, x_out, ld_out, _ = _flow_io(z, D, log_det, x_out, False)
     ok = _launch("jf_amlp_gf_chain_fwd_f64", "K%d_H%d_N%d_D%d_r%d" % (K1, H, u2.shape[0], D, r2),
-                 (_ptr(inp), inp.stride(0), _ptr(v1c), _ptr(ws[0]), _ptr(ws[1]), _ptr(ws[2]), _ptr(ws[3]), _ptr(ws[4]), K1, H, r1, r2, _ptr(z), z.stride(0),
-                  _ptr(log_det), B, D, n_layers, layer_array, _ptr(x_out), x_out.stride(0), _ptr(ld_out), _ptr(status)), dev, unsupported_ok=True)
+                 (_ptr(inp), inp.stride(0)) + w_args + (K1, H, r1, r2, _ptr(z), z.stride(0), _ptr(log_det), B, D, n_layers, layer_array, _ptr(x_out),
+                                                        x_out.stride(0), _ptr(ld_out), _ptr(status)), dev, unsupported_ok=True)
     return (x_out, ld_out) if ok else None
 
 
@@ -1016,14 +1079,11 @@ def amlp2(inp, v1, u1, b1, v2, u2, b2):
     dev = require_device(inp, v1, u1, b1, v2, u2, b2)
     inp = _rowmajor(inp)
     B, K1 = inp.shape
-    H, r2, N = v2.shape[1], v2.shape[0], u2.shape[0]
-    r1 = 0 if v1 is None else v1.shape[0]
-    ws = [t.contiguous() for t in (u1, b1, v2, u2, b2)]
-    v1c = None if v1 is None else v1.contiguous()
+    ws, w_args, r1, r2, H = _amlp_weights(v1, u1, b1, v2, u2, b2)
+    N = u2.shape[0]
     out = torch.empty((B, N), dtype=inp.dtype, device=inp.device)
     _launch("jf_amlp2" + _suffix(inp), "K%d_H%d_N%d_r%d" % (K1, H, N, r2),
-            (_ptr(inp), inp.stride(0), _ptr(v1c), _ptr(ws[0]), _ptr(ws[1]), _ptr(ws[2]), _ptr(ws[3]), _ptr(ws[4]), B, K1, H, r1, r2, N, _ptr(out),
-             out.stride(0)), dev)
+            (_ptr(inp), inp.stride(0)) + w_args + (B, K1, H, r1, r2, N, _ptr(out), out.stride(0)), dev)
     return out
 
 
@@ -1070,74 +1130,40 @@ def cond_gf_chain_inv_split(inp, w1, b1, packed, x, log_det, layer_array, n_laye
     pre_ld / pre_blp (lists of (B,) tensors, with want_base_logp): this block is the last of its pdf -- the launch also adds the earlier blocks'
     log-dets / base log-probs in front of its own (list order) and returns (x_out, log_det total, base_logp total, total log-prob): the sums of
     combine_rows without its launch.  Returns None when the segment-input kernel that does this is not the one in use."""
-    seg = None
     if pre_ld is not None or pre_blp is not None:
         if not (want_base_logp and kind == "split16" and aux is None and isinstance(inp, SegInput) and inp.in_place_ok and inp.dtype == torch.float32
                 and len(pre_ld or []) <= COND_GF_MAX_PRE and len(pre_blp or []) <= COND_GF_MAX_PRE):
             return None
-    if isinstance(inp, SegInput):
-        if kind == "split16" and inp.in_place_ok and inp.dtype == torch.float32:
-            seg = inp                                      # read in place by jf_cond_gf_chain_split3_f32
-            inp = seg.segments[0][0]
-        else:
-            inp = inp.materialize()
+    # a SegInput is read in place by jf_cond_gf_chain_split3_f32 (float32, "split16" only)
+    (inp, w1, b1, seg), head, B, K1, H = _mlp_head(inp, w1, b1, "cond_gf_chain_inv_split", torch.float32, torch.float32 if kind == "split16" else None)
     dev = require_device(inp, w1, b1, packed, x, log_det, x_out, base_logp_in, status, *(seg.tensors() if seg else []))
-    inp, w1, x = _rowmajor(inp), _rowmajor(w1), _rowmajor(x)
-    B, K1 = seg.shape if seg else inp.shape
-    H = w1.shape[0]
-    if x.shape[0] != B or x.shape[1] != D or w1.shape[1] != K1 or b1.shape[0] != H:
+    x = _rowmajor(x)
+    if x.shape[0] != B or x.shape[1] != D:
         raise ValueError("cond_gf_chain_inv_split: inconsistent shapes")
-    if any(t.dtype != torch.float32 for t in (inp, w1, b1, x)) or packed.dtype != torch.uint8:
+    if x.dtype != torch.float32 or packed.dtype != torch.uint8:
         raise TypeError("cond_gf_chain_inv_split: float32 inputs and a uint8 packed image expected")
-    if log_det is not None:
-        log_det = log_det.contiguous()
-    if x_out is None:
-        x_out = torch.empty((B, D), dtype=x.dtype, device=x.device)
-    ld_out = torch.empty((B,), dtype=x.dtype, device=x.device)
-    blp_out = torch.empty((B,), dtype=x.dtype, device=x.device) if want_base_logp else None
-    if kind == "split16":
-        if aux is not None and (aux.dtype != torch.float32 or aux.numel() < n_layers * B * 20 or not aux.is_contiguous()):
-            raise ValueError("cond_gf_chain_inv_split: aux = cond_gf_aux(B, n_layers)")
-        if seg is not None:
-            arr = seg.c_array()
-            lists, total = (None, None), None
-            if pre_ld is not None or pre_blp is not None:
-                def lst(items):
-                    r = jf_row_list()
-                    r.n = len(items)
-                    for i, t in enumerate(items):
-                        if t.dtype != torch.float32 or t.shape != (B,) or not t.is_contiguous():
-                            raise ValueError("cond_gf_chain_inv_split: pre_ld / pre_blp entries are contiguous float32 (B,) tensors")
-                        r.p[i] = _ptr(t)
-                    return r
-                require_device(x, *(list(pre_ld or []) + list(pre_blp or [])))
-                lists = (lst(list(pre_ld or [])), lst(list(pre_blp or [])))
-                total = torch.empty((B,), dtype=x.dtype, device=x.device)
-            _launch("jf_cond_gf_chain_split3_f32", "K%d_H%d_L%d_D%d" % (K1, H, n_layers, D),
-                    (DIR_INV, SPLIT_F16X2, arr, len(seg.segments), _ptr(w1), w1.stride(0), _ptr(b1.contiguous()), _ptr(packed), K1, H, _ptr(x), x.stride(0),
-                     _ptr(log_det), B, D, n_layers, layer_array, _ptr(x_out), x_out.stride(0), _ptr(ld_out), _ptr(base_logp_in), _ptr(blp_out), _ptr(aux),
-                     None if lists[0] is None else ctypes.byref(lists[0]), None if lists[1] is None else ctypes.byref(lists[1]), _ptr(total),
-                     _ptr(status)), dev)
-            if total is not None:
-                return x_out, ld_out, blp_out, total
-            return (x_out, ld_out, blp_out) if want_base_logp else (x_out, ld_out)
-        _launch("jf_cond_gf_chain_split2_f32", "K%d_H%d_L%d_D%d" % (K1, H, n_layers, D),
-                (DIR_INV, SPLIT_F16X2, _ptr(inp), inp.stride(0), _ptr(w1), w1.stride(0), _ptr(b1.contiguous()), _ptr(packed), K1, H, _ptr(x), x.stride(0),
-                 _ptr(log_det), B, D, n_layers, layer_array, _ptr(x_out), x_out.stride(0), _ptr(ld_out), _ptr(base_logp_in), _ptr(blp_out), _ptr(aux),
-                 _ptr(status)), dev)
-        return (x_out, ld_out, blp_out) if want_base_logp else (x_out, ld_out)
-    if aux is not None:
-        if kind != "split" or aux.dtype != torch.float32 or aux.numel() < n_layers * B * 20 or not aux.is_contiguous():
-            raise ValueError("cond_gf_chain_inv_split: aux needs the 'split' kernel and cond_gf_aux(B, n_layers)")
-        _launch("jf_cond_gf_chain_inv_split_save_f32", "K%d_H%d_L%d_D%d" % (K1, H, n_layers, D),
-                (_ptr(inp), inp.stride(0), _ptr(w1), w1.stride(0), _ptr(b1.contiguous()), _ptr(packed), K1, H, _ptr(x), x.stride(0), _ptr(log_det),
-                 B, D, n_layers, layer_array, _ptr(x_out), x_out.stride(0), _ptr(ld_out), _ptr(base_logp_in), _ptr(blp_out), _ptr(aux),
-                 _ptr(status)), dev)
-        return (x_out, ld_out, blp_out) if want_base_logp else (x_out, ld_out)
-    _launch(_COND_GF_PACK[kind][2], "K%d_H%d_L%d_D%d" % (K1, H, n_layers, D),
-            (_ptr(inp), inp.stride(0), _ptr(w1), w1.stride(0), _ptr(b1.contiguous()), _ptr(packed), K1, H, _ptr(x), x.stride(0), _ptr(log_det), B, D,
-             n_layers, layer_array, _ptr(x_out), x_out.stride(0), _ptr(ld_out), _ptr(base_logp_in), _ptr(blp_out), _ptr(status)), dev)
-    return (x_out, ld_out, blp_out) if want_base_logp else (x_out, ld_out)
+    log_det, x_out, ld_out, blp_out = _flow_io(x, D, log_det, x_out, want_base_logp)
+    if aux is not None and (kind not in _COND_GF_PACK or aux.dtype != torch.float32 or aux.numel() < n_layers * B * 20 or not aux.is_contiguous()):
+        raise ValueError("cond_gf_chain_inv_split: aux needs the 'split' or 'split16' kernel and cond_gf_aux(B, n_layers)")
+    tag = "K%d_H%d_L%d_D%d" % (K1, H, n_layers, D)
+    # every kernel of the block: [direction, arithmetic,] these arguments, [aux,] [the earlier blocks' rows and the total,] the status words
+    args = head + (_ptr(packed), K1, H, _ptr(x), x.stride(0), _ptr(log_det), B, D, n_layers, layer_array, _ptr(x_out), x_out.stride(0), _ptr(ld_out),
+                   _ptr(base_logp_in), _ptr(blp_out))
+    if seg is not None:
+        la = lb = total = None
+        if pre_ld is not None or pre_blp is not None:
+            la, lb, total = _pre_sums(pre_ld, pre_blp, x, "cond_gf_chain_inv_split")
+        _launch("jf_cond_gf_chain_split3_f32", tag, (DIR_INV, SPLIT_F16X2) + args
+                + (_ptr(aux), None if la is None else ctypes.byref(la), None if lb is None else ctypes.byref(lb), _ptr(total), _ptr(status)), dev)
+        if total is not None:
+            return x_out, ld_out, blp_out, total
+    elif kind == "split16":
+        _launch("jf_cond_gf_chain_split2_f32", tag, (DIR_INV, SPLIT_F16X2) + args + (_ptr(aux), _ptr(status)), dev)
+    elif aux is not None:
+        _launch("jf_cond_gf_chain_inv_split_save_f32", tag, args + (_ptr(aux), _ptr(status)), dev)
+    else:
+        _launch(_COND_GF_PACK[kind][2], tag, args + (_ptr(status),), dev)
+    return _flow_result(x_out, ld_out, blp_out, want_base_logp)
 
 
 COND_GF_SLOTS = 36                   # parameter slots per coordinate lane and layer in the packed gradient rows (csrc/jf_cond_regs.h)
@@ -1185,25 +1211,21 @@ def cond_gf_chain_inv_split_bwd(inp, w1, b1, packed, packed_t, z, aux, layer_arr
     """adjoint of cond_gf_chain_inv_split(..., aux=aux) in one launch -> (g_x (B, D), g_pp (B, n_layers * 144) packed parameter-row gradient,
     h (B, H) hidden activations, g_h (B, H)[, max |g_pp| as a 1-element tensor]); see include/jammy_hip.h."""
     dev = require_device(inp, w1, b1, packed, packed_t, z, aux, g_xout, g_ld, g_blp)
-    inp, w1, z = _rowmajor(inp), _rowmajor(w1), _rowmajor(z)
-    B, K1 = inp.shape
-    H = w1.shape[0]
-    if z.shape[0] != B or z.shape[1] != D or w1.shape[1] != K1 or b1.shape[0] != H or aux.numel() < n_layers * B * 20:
+    z = _rowmajor(z)
+    held, head, B, K1, H = _mlp_head(inp, w1, b1, "cond_gf_chain_inv_split_bwd", torch.float32)
+    if z.shape[0] != B or z.shape[1] != D or aux.numel() < n_layers * B * 20:
         raise ValueError("cond_gf_chain_inv_split_bwd: inconsistent shapes")
-    if any(t is not None and t.dtype != torch.float32 for t in (inp, w1, b1, z, aux, g_xout, g_ld, g_blp)):
+    if any(t is not None and t.dtype != torch.float32 for t in (z, aux, g_xout, g_ld, g_blp)):
         raise TypeError("cond_gf_chain_inv_split_bwd: float32 only")
-    g_xout = None if g_xout is None else _rowmajor(g_xout)
-    g_ld = None if g_ld is None else g_ld.contiguous()
-    g_blp = None if g_blp is None else g_blp.contiguous()
+    held_g, g_args = _cotangents(g_xout, g_ld, g_blp)
     g_x = torch.empty((B, D), dtype=z.dtype, device=z.device)
     g_pp = torch.empty((B, n_layers * 4 * COND_GF_SLOTS), dtype=z.dtype, device=z.device)
     h = torch.empty((B, H), dtype=z.dtype, device=z.device)
     g_h = torch.empty((B, H), dtype=z.dtype, device=z.device)
     absmax = torch.zeros((1,), dtype=z.dtype, device=z.device) if want_absmax else None
     _launch("jf_cond_gf_chain_inv_split_bwd_f32", "K%d_H%d_L%d_D%d" % (K1, H, n_layers, D),
-            (_ptr(inp), inp.stride(0), _ptr(w1), w1.stride(0), _ptr(b1.contiguous()), _ptr(packed), _ptr(packed_t), K1, H, _ptr(z), z.stride(0),
-             _ptr(aux), B, D, n_layers, layer_array, _ptr(g_xout), 0 if g_xout is None else g_xout.stride(0), _ptr(g_ld), _ptr(g_blp),
-             _ptr(g_x), g_x.stride(0), _ptr(g_pp), g_pp.stride(0), _ptr(h), h.stride(0), _ptr(g_h), g_h.stride(0), _ptr(absmax)), dev)
+            head + (_ptr(packed), _ptr(packed_t), K1, H, _ptr(z), z.stride(0), _ptr(aux), B, D, n_layers, layer_array) + g_args
+            + (_ptr(g_x), g_x.stride(0), _ptr(g_pp), g_pp.stride(0), _ptr(h), h.stride(0), _ptr(g_h), g_h.stride(0), _ptr(absmax)), dev)
     return (g_x, g_pp, h, g_h, absmax) if want_absmax else (g_x, g_pp, h, g_h)
 
 
@@ -1239,40 +1261,23 @@ def linear_wgrad_split16(g, inp, g_absmax, in_exp=14, want_bias=True, rows=None)
 def cond_gf_chain_fwd_split(inp, w1, b1, packed, z, log_det, layer_array, n_layers, D, x_out=None, status=None, kind="split"):
     """sampling direction of a conditional e-block in one launch (amortisation MLP + bisection / Newton solves on register-resident
     parameters); `packed`: the "split" / "split16" image of cond_gf_pack (`kind` names which)."""
-    seg = None
-    if isinstance(inp, SegInput):
-        if kind == "split16" and inp.in_place_ok and inp.dtype == torch.float32:
-            seg = inp                                      # read in place by jf_cond_gf_chain_split3_f32 (the earlier blocks' samples where they are)
-            inp = seg.segments[0][0]
-        else:
-            inp = inp.materialize()
+    # a SegInput is read in place by jf_cond_gf_chain_split3_f32 (float32, "split16" only): the earlier blocks' samples where they are
+    (inp, w1, b1, seg), head, B, K1, H = _mlp_head(inp, w1, b1, "cond_gf_chain_fwd_split", torch.float32, torch.float32 if kind == "split16" else None)
     dev = require_device(inp, w1, b1, packed, z, log_det, x_out, status, *(seg.tensors() if seg else []))
-    inp, w1, z = _rowmajor(inp), _rowmajor(w1), _rowmajor(z)
-    B, K1 = seg.shape if seg else inp.shape
-    H = w1.shape[0]
-    if z.shape[0] != B or z.shape[1] != D or w1.shape[1] != K1 or b1.shape[0] != H:
+    z = _rowmajor(z)
+    if z.shape[0] != B or z.shape[1] != D:
         raise ValueError("cond_gf_chain_fwd_split: inconsistent shapes")
-    if any(t.dtype != torch.float32 for t in (inp, w1, b1, z)) or packed.dtype != torch.uint8:
+    if z.dtype != torch.float32 or packed.dtype != torch.uint8:
         raise TypeError("cond_gf_chain_fwd_split: float32 inputs and a uint8 packed image expected")
-    if log_det is not None:
-        log_det = log_det.contiguous()
-    if x_out is None:
-        x_out = torch.empty((B, D), dtype=z.dtype, device=z.device)
-    ld_out = torch.empty((B,), dtype=z.dtype, device=z.device)
-    if seg is not None:
-        _launch("jf_cond_gf_chain_split3_f32", "K%d_H%d_L%d_D%d_fwd" % (K1, H, n_layers, D),
-                (DIR_FWD, SPLIT_F16X2, seg.c_array(), len(seg.segments), _ptr(w1), w1.stride(0), _ptr(b1.contiguous()), _ptr(packed), K1, H, _ptr(z),
-                 z.stride(0), _ptr(log_det), B, D, n_layers, layer_array, _ptr(x_out), x_out.stride(0), _ptr(ld_out), None, None, None, None, None, None,
-                 _ptr(status)), dev)
-        return x_out, ld_out
-    if kind == "split16":
-        _launch("jf_cond_gf_chain_split2_f32", "K%d_H%d_L%d_D%d_fwd" % (K1, H, n_layers, D),
-                (DIR_FWD, SPLIT_F16X2, _ptr(inp), inp.stride(0), _ptr(w1), w1.stride(0), _ptr(b1.contiguous()), _ptr(packed), K1, H, _ptr(z), z.stride(0),
-                 _ptr(log_det), B, D, n_layers, layer_array, _ptr(x_out), x_out.stride(0), _ptr(ld_out), None, None, None, _ptr(status)), dev)
-        return x_out, ld_out
-    _launch("jf_cond_gf_chain_fwd_split_f32", "K%d_H%d_L%d_D%d" % (K1, H, n_layers, D),
-            (_ptr(inp), inp.stride(0), _ptr(w1), w1.stride(0), _ptr(b1.contiguous()), _ptr(packed), K1, H, _ptr(z), z.stride(0), _ptr(log_det), B, D,
-             n_layers, layer_array, _ptr(x_out), x_out.stride(0), _ptr(ld_out), _ptr(status)), dev)
+    log_det, x_out, ld_out, _ = _flow_io(z, D, log_det, x_out, False)
+    tag = "K%d_H%d_L%d_D%d" % (K1, H, n_layers, D)
+    args = head + (_ptr(packed), K1, H, _ptr(z), z.stride(0), _ptr(log_det), B, D, n_layers, layer_array, _ptr(x_out), x_out.stride(0), _ptr(ld_out))
+    if seg is not None:        # (the two-direction kernels: no base log-prob, aux, earlier blocks' rows or total when sampling)
+        _launch("jf_cond_gf_chain_split3_f32", tag + "_fwd", (DIR_FWD, SPLIT_F16X2) + args + (None,) * 6 + (_ptr(status),), dev)
+    elif kind == "split16":
+        _launch("jf_cond_gf_chain_split2_f32", tag + "_fwd", (DIR_FWD, SPLIT_F16X2) + args + (None,) * 3 + (_ptr(status),), dev)
+    else:
+        _launch("jf_cond_gf_chain_fwd_split_f32", tag, args + (_ptr(status),), dev)
     return x_out, ld_out
 
 
@@ -1407,9 +1412,9 @@ def mlp2_small_bwd(x, w1, b1, w2, g):
     """gradients (g_w1, g_b1, g_w2, g_b2) of out = tanh(x w1^T + b1) w2^T + b2 for upstream g (B, N), narrow heads only (K1 <= 32, N <= 16 --
     or K1 <= 8, N <= 64 (float64: 48) -- H <= 128): one launch that recomputes the hidden activations (jf_mlp2_small_bwd); no input gradient."""
     dev = require_device(x, w1, b1, w2, g)
-    x, w1, w2, g = _rowmajor(x), _rowmajor(w1), _rowmajor(w2), _rowmajor(g)
-    B, K1 = x.shape
-    H, N = w1.shape[0], w2.shape[0]
+    (x, w1, b1, _), head, B, K1, H = _mlp_head(x, w1, b1)
+    w2, g = _rowmajor(w2), _rowmajor(g)
+    N = w2.shape[0]
     if B == 0:                                         # no rows: the kernels do not launch, the gradients are exact zeros
         z = torch.zeros((H, K1 + 1 + N), dtype=x.dtype, device=x.device)
         return z[:, :K1], z[:, K1], z[:, K1 + 1:].t(), torch.zeros((N,), dtype=x.dtype, device=x.device)
@@ -1417,8 +1422,7 @@ def mlp2_small_bwd(x, w1, b1, w2, g):
     slab = torch.empty((S, H, K1 + 1 + N), dtype=x.dtype, device=x.device)
     slab_b2 = torch.empty((S, N), dtype=x.dtype, device=x.device)
     _launch("jf_mlp2_small_bwd" + _suffix(x), "K%d_H%d_N%d" % (K1, H, N),
-            (_ptr(x), x.stride(0), _ptr(w1), w1.stride(0), _ptr(b1.contiguous()), _ptr(w2), w2.stride(0), _ptr(g), g.stride(0), B, K1, H, N, _ptr(slab),
-             _ptr(slab_b2)), dev)
+            head + (_ptr(w2), w2.stride(0), _ptr(g), g.stride(0), B, K1, H, N, _ptr(slab), _ptr(slab_b2)), dev)
     # the slab's (H, K1 | 1 | N) columns and the b2 slab -> [g_w1 (H, K1) | g_b1 (H) | g_w2 (N, H) | g_b2 (N)], every piece contiguous
     def build():
         h, c = np.meshgrid(np.arange(H), np.arange(K1 + 1 + N), indexing="ij")
@@ -1433,16 +1437,14 @@ def mlp_hidden_bwd(x, w1, b1, g_hidden):
     """(g_w1, g_b1) of h = tanh(x w1^T + b1) for the gradient g_hidden (B, H) with respect to h: tanh derivative + first-layer weight / bias
     gradient in one launch (jf_mlp_hidden_bwd; K1 <= 32, H <= 128), the activations recomputed from x"""
     dev = require_device(x, w1, b1, g_hidden)
-    x, w1, g_hidden = _rowmajor(x), _rowmajor(w1), _rowmajor(g_hidden)
-    B, K1 = x.shape
-    H = w1.shape[0]
+    (x, w1, b1, _), head, B, K1, H = _mlp_head(x, w1, b1)
+    g_hidden = _rowmajor(g_hidden)
     if B == 0:
         z = torch.zeros((H, K1 + 1), dtype=x.dtype, device=x.device)
         return z[:, :K1], z[:, K1]
     S = int(lib().jf_mlp2_small_bwd_slabs(B))
     slab = torch.empty((S, H, K1 + 1), dtype=x.dtype, device=x.device)
-    _launch("jf_mlp_hidden_bwd" + _suffix(x), "K%d_H%d" % (K1, H),
-            (_ptr(x), x.stride(0), _ptr(w1), w1.stride(0), _ptr(b1.contiguous()), _ptr(g_hidden), g_hidden.stride(0), B, K1, H, _ptr(slab)), dev)
+    _launch("jf_mlp_hidden_bwd" + _suffix(x), "K%d_H%d" % (K1, H), head + (_ptr(g_hidden), g_hidden.stride(0), B, K1, H, _ptr(slab)), dev)
     def build():
         h, c = np.meshgrid(np.arange(H), np.arange(K1 + 1), indexing="ij")
         return np.where(c < K1, h * K1 + c, H * K1 + h).reshape(-1)
@@ -1488,16 +1490,10 @@ class SegInput:
     MAX_IN_PLACE = 4          # csrc/jf_cond_in.h: JF_COND_IN_MAX
 
     def __init__(self, segments, B, dtype, device):
-        self.segments = [(_rowmajor(t), kind) for t, kind in segments]
-        self.width = sum(t.shape[1] if kind == 0 else kind + 1 for t, kind in self.segments)
+        self.segments, self.width = _segments(segments, B, dtype, "SegInput")
         self.shape = (B, self.width)
         self.dtype, self.device = dtype, device
         self._rows = None
-        for i, (t, kind) in enumerate(self.segments):
-            if t.dtype != dtype or t.shape[0] != B:
-                raise TypeError("SegInput: segment %d has dtype %s / %d rows, expected %s / %d" % (i, t.dtype, t.shape[0], dtype, B))
-            if kind != 0 and t.shape[1] != kind:
-                raise ValueError("SegInput: an S%d segment needs %d intrinsic columns" % (kind, kind))
 
     @property
     def in_place_ok(self):
@@ -1509,10 +1505,7 @@ class SegInput:
         return self.dtype == torch.float32 or all(kind == 0 for _, kind in self.segments)
 
     def c_array(self):
-        arr = (jf_cond_segment * len(self.segments))()
-        for i, (t, kind) in enumerate(self.segments):
-            arr[i] = jf_cond_segment(_ptr(t), t.stride(0), kind, t.shape[1])
-        return arr
+        return _segment_array(self.segments)
 
     def tensors(self):
         return [t for t, _ in self.segments]
@@ -1533,21 +1526,10 @@ def conditioning_rows(segments, B, dtype, device):
     Returns the (B, sum of output widths) row block cat[...] in ONE launch (the amortisation MLPs read prefixes of it)."""
     if not 1 <= len(segments) <= JF_MAX_SEGMENTS:
         raise ValueError("conditioning_rows: 1..%d segments" % JF_MAX_SEGMENTS)
-    arr = (jf_cond_segment * len(segments))()
-    width = 0
-    keep = []
     dev = require_device(*[t for t, _ in segments])
-    for i, (t, kind) in enumerate(segments):
-        t = _rowmajor(t)
-        if t.dtype != dtype or t.shape[0] != B:
-            raise TypeError("conditioning_rows: segment %d has dtype %s / %d rows, expected %s / %d" % (i, t.dtype, t.shape[0], dtype, B))
-        if kind != 0 and t.shape[1] != kind:
-            raise ValueError("conditioning_rows: an S%d segment needs %d intrinsic columns" % (kind, kind))
-        keep.append(t)
-        arr[i] = jf_cond_segment(_ptr(t), t.stride(0), kind, t.shape[1])
-        width += t.shape[1] if kind == 0 else kind + 1
+    segments, width = _segments(segments, B, dtype, "conditioning_rows")
     out = torch.empty((B, width), dtype=dtype, device=device)
-    _launch("jf_conditioning_rows" + _suffix(out), "", (arr, len(segments), B, _ptr(out), out.stride(0)), dev)
+    _launch("jf_conditioning_rows" + _suffix(out), "", (_segment_array(segments), len(segments), B, _ptr(out), out.stride(0)), dev)
     return out
 
 
@@ -1609,19 +1591,12 @@ def pair_logmeanexp(kind, x, params, n_params, n_groups, S, i0, i1, layers, dim,
         raise ValueError("pair_logmeanexp: expected targets of shape (%d, %d), got %s" % (rows, dim, tuple(x.shape)))
     if not (0 <= i0 <= i1 <= S):
         raise ValueError("pair_logmeanexp: bad target range [%d, %d) for S = %d" % (i0, i1, S))
-    n_layers, need = len(layers), int(n_params)
-    pptr, pstride = None, 0
-    if params is not None and params.shape[1] > 0:
-        params = _rowmajor(params)
-        if params.dtype != x.dtype:
-            raise TypeError("parameter dtype %s != input dtype %s" % (params.dtype, x.dtype))
-        if params.shape[0] not in (1, rows):
-            raise ValueError("pair_logmeanexp: parameters must have 1 or %d rows, got %d" % (rows, params.shape[0]))
-        if params.shape[1] != need:
-            raise ValueError("pair_logmeanexp: the chain takes %d parameters per row, got %d" % (need, params.shape[1]))
-        pptr, pstride = _ptr(params), (0 if params.shape[0] == 1 and rows != 1 else params.stride(0))
-    elif need != 0:
-        raise ValueError("pair_logmeanexp: the chain takes %d parameters per row, got none" % need)
+    n_layers = len(layers)
+    params, pptr, pstride, pb = _param_rows(params, rows, x.dtype, "pair_logmeanexp")
+    if (0 if params is None else params.shape[1]) != int(n_params):
+        raise ValueError("pair_logmeanexp: the chain takes %d parameters per row, got %s" % (n_params, "none" if params is None else params.shape[1]))
+    if pb == 1 and rows != 1:
+        pstride = 0          # these entry points take no param_batch: one permanent row is a row stride of 0
     if add is not None:
         add = add.contiguous().reshape(-1)
         if add.dtype != x.dtype or add.shape[0] != rows:
@@ -1636,7 +1611,7 @@ def pair_logmeanexp(kind, x, params, n_params, n_groups, S, i0, i1, layers, dim,
         ok = _launch("jf_pair_gf" + suf, "pair", (_ptr(x), x.stride(0), pptr, pstride, n_groups, S, i0, i1, dim, n_layers, layers, _ptr(add),
                                                   _ptr(tile), _ptr(out), _ptr(status)), dev, unsupported_ok=True)
     else:
-        arr = (MCHAIN_LAYER_TYPES[kind] * n_layers)(*layers)
+        arr = mchain_layer_array(kind, layers)
         ok = _launch("jf_pair_mchain" + suf, "pair", (ord(kind), _ptr(x), x.stride(0), pptr, pstride, n_groups, S, i0, i1, n_layers,
                                                       ctypes.cast(arr, ctypes.c_void_p), _ptr(add), _ptr(tile), _ptr(out), _ptr(status)), dev,
                      unsupported_ok=True)
@@ -1694,29 +1669,11 @@ def mchain(fam, direction, x, log_det, params, layer_structs, dim, x_out=None, b
     B = x.shape[0]
     if x.shape[1] != dim:
         raise ValueError("expected %d target columns, got %d" % (dim, x.shape[1]))
-    pb = 1
-    if params is not None and params.shape[1] > 0:
-        params = _rowmajor(params)
-        if params.dtype != x.dtype:
-            raise TypeError("parameter dtype %s != input dtype %s" % (params.dtype, x.dtype))
-        if params.shape[0] not in (1, B):
-            raise ValueError("extra_inputs must have 1 or B=%d rows, got %d" % (B, params.shape[0]))
-        pb = 1 if params.shape[0] == 1 else B
-        pptr, pstride = _ptr(params), params.stride(0)
-    else:
-        pptr, pstride = None, 0
-    if log_det is not None:
-        log_det = log_det.contiguous()
-        if log_det.dtype != x.dtype or log_det.shape[0] != B:
-            raise ValueError("log_det must be a (B,) tensor of the input dtype")
-    if x_out is None:
-        x_out = torch.empty((B, dim), dtype=x.dtype, device=x.device)
-    ld_out = torch.empty((B,), dtype=x.dtype, device=x.device)
-    blp_out = torch.empty((B,), dtype=x.dtype, device=x.device) if want_base_logp else None
+    params, pptr, pstride, pb = _param_rows(params, B, x.dtype, "mchain")
+    log_det, x_out, ld_out, blp_out = _flow_io(x, dim, log_det, x_out, want_base_logp, check_log_det=True)
     n = len(layer_structs)
-    arr = (MCHAIN_LAYER_TYPES[fam] * n)(*layer_structs)
+    arr = mchain_layer_array(fam, layer_structs)
     suf = _suffix(x)
-    name = "jf_%s_chain_%s%s" % (fam, direction, suf)
     if bins is None and BINS_LOG is not None and fam in ("r", "o", "f"):
         n_search = sum(1 if fam in "ro" else (L.n_vertical + L.n_circular) for L in layer_structs)
         if n_search:
@@ -1724,28 +1681,18 @@ def mchain(fam, direction, x, log_det, params, layer_structs, dim, x_out=None, b
             BINS_LOG.append(bins)
     if bins is not None:
         assert bins.dtype == torch.int64 and bins.dim() == 2 and bins.shape[0] == B and bins.stride(1) == 1
+    tag = "bcast" if pb == 1 else "per-sample"
+    args = (_ptr(x), x.stride(0), _ptr(log_det), pptr, pstride, pb, B, n, arr, _ptr(x_out), x_out.stride(0), _ptr(ld_out), _ptr(base_logp_in),
+            _ptr(blp_out))
+    tail = (_ptr(bins), bins.stride(0) if bins is not None else 0, _ptr(status))
     if pre_ld is not None or pre_blp is not None:
         if direction != "inv" or not want_base_logp:
             raise ValueError("mchain: pre_ld / pre_blp need direction 'inv' and want_base_logp")
-        def lst(items):
-            r = jf_row_list()
-            r.n = len(items)
-            for i, t in enumerate(items):
-                if t.dtype != x.dtype or t.shape != (B,) or not t.is_contiguous():
-                    raise ValueError("mchain: pre_ld / pre_blp entries are contiguous (B,) tensors of the input dtype")
-                r.p[i] = _ptr(t)
-            return r
-        require_device(x, *(list(pre_ld or []) + list(pre_blp or [])))
-        la, lb = lst(list(pre_ld or [])), lst(list(pre_blp or []))
-        total = torch.empty((B,), dtype=x.dtype, device=x.device)
-        _launch("jf_%s_chain_inv_sum%s" % (fam, suf), "bcast" if pb == 1 else "per-sample",
-                (_ptr(x), x.stride(0), _ptr(log_det), pptr, pstride, pb, B, n, arr, _ptr(x_out), x_out.stride(0), _ptr(ld_out), _ptr(base_logp_in),
-                 _ptr(blp_out), ctypes.byref(la), ctypes.byref(lb), _ptr(total), _ptr(bins), bins.stride(0) if bins is not None else 0, _ptr(status)), dev)
+        la, lb, total = _pre_sums(pre_ld, pre_blp, x, "mchain")
+        _launch("jf_%s_chain_inv_sum%s" % (fam, suf), tag, args + (ctypes.byref(la), ctypes.byref(lb), _ptr(total)) + tail, dev)
         return x_out, ld_out, blp_out, total
-    _launch(name, "bcast" if pb == 1 else "per-sample",
-            (_ptr(x), x.stride(0), _ptr(log_det), pptr, pstride, pb, B, n, arr, _ptr(x_out), x_out.stride(0), _ptr(ld_out), _ptr(base_logp_in),
-             _ptr(blp_out), _ptr(bins), bins.stride(0) if bins is not None else 0, _ptr(status)), dev)
-    return (x_out, ld_out, blp_out) if want_base_logp else (x_out, ld_out)
+    _launch("jf_%s_chain_%s%s" % (fam, direction, suf), tag, args + tail, dev)
+    return _flow_result(x_out, ld_out, blp_out, want_base_logp)
 
 
 COND_MCHAIN_FAMILIES, COND_MCHAIN_MAX_PARAMS = "romf", 64
@@ -1754,51 +1701,34 @@ COND_MCHAIN_FAMILIES, COND_MCHAIN_MAX_PARAMS = "romf", 64
 def cond_mchain_inv(fam, inp, w1, b1, w2, b2, x, log_det, layer_structs, dim, x_out=None, base_logp_in=None, want_base_logp=False, status=None):
     """default amortisation MLP (Linear-tanh-Linear) + the chain of manifold layers of family `fam` it parametrises in ONE launch"""
     dev = require_device(inp, w1, b1, w2, b2, x, log_det, x_out, base_logp_in, status)
-    inp, w1, w2, x = _rowmajor(inp), _rowmajor(w1), _rowmajor(w2), _rowmajor(x)
-    B, K1 = inp.shape
-    H = w1.shape[0]
-    if x.shape != (B, dim) or w1.shape[1] != K1 or w2.shape[1] != H or b1.shape[0] != H or b2.shape[0] != w2.shape[0]:
+    x = _rowmajor(x)
+    held, head, B, K1, H = _mlp_head(inp, w1, b1, "cond_mchain_inv", x.dtype)
+    held2, second, N = _mlp_second(w2, b2, H, "cond_mchain_inv", x.dtype)
+    if x.shape != (B, dim):
         raise ValueError("cond_mchain_inv: inconsistent shapes")
-    if any(t.dtype != x.dtype for t in (inp, w1, b1, w2, b2)):
-        raise TypeError("cond_mchain_inv: dtype mismatch")
-    if log_det is not None:
-        log_det = log_det.contiguous()
-    if x_out is None:
-        x_out = torch.empty((B, dim), dtype=x.dtype, device=x.device)
-    ld_out = torch.empty((B,), dtype=x.dtype, device=x.device)
-    blp_out = torch.empty((B,), dtype=x.dtype, device=x.device) if want_base_logp else None
-    n = len(layer_structs)
-    arr = (MCHAIN_LAYER_TYPES[fam] * n)(*layer_structs)
-    ok = _launch("jf_cond_%s_chain_inv%s" % (fam, _suffix(x)), "K%d_H%d_N%d" % (K1, H, w2.shape[0]),
-            (_ptr(inp), inp.stride(0), _ptr(w1), w1.stride(0), _ptr(b1.contiguous()), _ptr(w2), w2.stride(0), _ptr(b2.contiguous()), K1, H, _ptr(x),
-             x.stride(0), _ptr(log_det), B, n, arr, _ptr(x_out), x_out.stride(0), _ptr(ld_out), _ptr(base_logp_in), _ptr(blp_out), _ptr(status)), dev,
-            unsupported_ok=True)
+    log_det, x_out, ld_out, blp_out = _flow_io(x, dim, log_det, x_out, want_base_logp)
+    ok = _launch("jf_cond_%s_chain_inv%s" % (fam, _suffix(x)), "K%d_H%d_N%d" % (K1, H, N),
+                 head + second + (K1, H, _ptr(x), x.stride(0), _ptr(log_det), B, len(layer_structs), mchain_layer_array(fam, layer_structs),
+                                  _ptr(x_out), x_out.stride(0), _ptr(ld_out), _ptr(base_logp_in), _ptr(blp_out), _ptr(status)), dev,
+                 unsupported_ok=True)
     if not ok:
         return None                                   # outside the fused kernel's limits (LDS budget): use the two-launch path
-    return (x_out, ld_out, blp_out) if want_base_logp else (x_out, ld_out)
+    return _flow_result(x_out, ld_out, blp_out, want_base_logp)
 
 
 def cond_mchain_fwd(fam, inp, w1, b1, w2, b2, z, log_det, layer_structs, dim, x_out=None, status=None):
     """sampling direction of cond_mchain_inv: default amortisation MLP + the manifold chain forwards in ONE launch -> (x, log_det), or None
     outside the fused kernel's limits"""
     dev = require_device(inp, w1, b1, w2, b2, z, log_det, x_out, status)
-    inp, w1, w2, z = _rowmajor(inp), _rowmajor(w1), _rowmajor(w2), _rowmajor(z)
-    B, K1 = inp.shape
-    H = w1.shape[0]
-    if z.shape != (B, dim) or w1.shape[1] != K1 or w2.shape[1] != H or b1.shape[0] != H or b2.shape[0] != w2.shape[0]:
+    z = _rowmajor(z)
+    held, head, B, K1, H = _mlp_head(inp, w1, b1, "cond_mchain_fwd", z.dtype)
+    held2, second, N = _mlp_second(w2, b2, H, "cond_mchain_fwd", z.dtype)
+    if z.shape != (B, dim):
         raise ValueError("cond_mchain_fwd: inconsistent shapes")
-    if any(t.dtype != z.dtype for t in (inp, w1, b1, w2, b2)):
-        raise TypeError("cond_mchain_fwd: dtype mismatch")
-    if log_det is not None:
-        log_det = log_det.contiguous()
-    if x_out is None:
-        x_out = torch.empty((B, dim), dtype=z.dtype, device=z.device)
-    ld_out = torch.empty((B,), dtype=z.dtype, device=z.device)
-    n = len(layer_structs)
-    arr = (MCHAIN_LAYER_TYPES[fam] * n)(*layer_structs)
-    ok = _launch("jf_cond_%s_chain_fwd%s" % (fam, _suffix(z)), "K%d_H%d_N%d" % (K1, H, w2.shape[0]),
-                 (_ptr(inp), inp.stride(0), _ptr(w1), w1.stride(0), _ptr(b1.contiguous()), _ptr(w2), w2.stride(0), _ptr(b2.contiguous()), K1, H, _ptr(z),
-                  z.stride(0), _ptr(log_det), B, n, arr, _ptr(x_out), x_out.stride(0), _ptr(ld_out), _ptr(status)), dev, unsupported_ok=True)
+    log_det, x_out, ld_out, _ = _flow_io(z, dim, log_det, x_out, False)
+    ok = _launch("jf_cond_%s_chain_fwd%s" % (fam, _suffix(z)), "K%d_H%d_N%d" % (K1, H, N),
+                 head + second + (K1, H, _ptr(z), z.stride(0), _ptr(log_det), B, len(layer_structs), mchain_layer_array(fam, layer_structs),
+                                  _ptr(x_out), x_out.stride(0), _ptr(ld_out), _ptr(status)), dev, unsupported_ok=True)
     return (x_out, ld_out) if ok else None
 
 
@@ -1809,75 +1739,48 @@ def t_layer(direction, x, log_det, params, struct, D, x_out=None, base_logp_in=N
     B = x.shape[0]
     if x.shape[1] != D:
         raise ValueError("expected %d target columns, got %d" % (D, x.shape[1]))
-    pb, pptr, pstride = 1, None, 0
-    if params is not None and params.shape[1] > 0:
-        params = _rowmajor(params)
-        if params.dtype != x.dtype or params.shape[0] not in (1, B):
-            raise ValueError("extra_inputs must be (1 | B, P) of the input dtype")
-        pb = 1 if params.shape[0] == 1 else B
-        pptr, pstride = _ptr(params), params.stride(0)
-    if log_det is not None:
-        log_det = log_det.contiguous()
-    if x_out is None:
-        x_out = torch.empty((B, D), dtype=x.dtype, device=x.device)
-    ld_out = torch.empty((B,), dtype=x.dtype, device=x.device)
-    blp_out = torch.empty((B,), dtype=x.dtype, device=x.device) if want_base_logp else None
+    params, pptr, pstride, pb = _param_rows(params, B, None, "t_layer")
+    if params is not None and params.dtype != x.dtype:           # (a dtype mismatch is a ValueError here, not _param_rows' TypeError)
+        raise ValueError("extra_inputs must be (1 | B, P) of the input dtype")
+    log_det, x_out, ld_out, blp_out = _flow_io(x, D, log_det, x_out, want_base_logp)
     _launch("jf_t_layer_%s%s" % (direction, _suffix(x)), "bcast" if pb == 1 else "per-sample",
             (_ptr(x), x.stride(0), _ptr(log_det), pptr, pstride, pb, B, D, ctypes.byref(struct), _ptr(x_out), x_out.stride(0), _ptr(ld_out),
              _ptr(base_logp_in), _ptr(blp_out), _ptr(status)), dev)
-    return (x_out, ld_out, blp_out) if want_base_logp else (x_out, ld_out)
+    return _flow_result(x_out, ld_out, blp_out, want_base_logp)
 
 
-def t_layer_inv_bwd(x, params, struct, D, g_xout, g_ld, g_blp, status=None):
+def _chain_inv_bwd(name, x, params, D, layers, g_xout, g_ld, g_blp, status):
+    """the launch t_layer_inv_bwd and mchain_inv_bwd share: `layers` is the argument between the row count and the upstream gradients
+    -> (g_x (B, D), g_params (B, P), (1, P) zeroed for the launch's atomics when one row is shared, or None without parameters)"""
     dev = require_device(x, params, g_xout, g_ld, g_blp, status)
     x = _rowmajor(x)
     B = x.shape[0]
-    P = 0 if params is None else params.shape[1]
-    pb, pptr, pstride, g_p = 1, None, 0, None
-    if P > 0:
-        params = _rowmajor(params)
-        pb = 1 if params.shape[0] == 1 else B
-        pptr, pstride = _ptr(params), params.stride(0)
+    params, pptr, pstride, pb = _param_rows(params, B)
+    g_p = None
+    if params is not None:
+        P = params.shape[1]
         g_p = torch.zeros((1, P), dtype=x.dtype, device=x.device) if pb == 1 else torch.empty((B, P), dtype=x.dtype, device=x.device)
-    if g_xout is not None:
-        g_xout = _rowmajor(g_xout)
-    g_ld = None if g_ld is None else g_ld.contiguous()
-    g_blp = None if g_blp is None else g_blp.contiguous()
+    held, g_args = _cotangents(g_xout, g_ld, g_blp)
     g_x = torch.empty((B, D), dtype=x.dtype, device=x.device)
-    _launch("jf_t_layer_inv_bwd" + _suffix(x), "bcast" if pb == 1 else "per-sample",
-            (_ptr(x), x.stride(0), pptr, pstride, pb, B, D, ctypes.byref(struct), _ptr(g_xout), g_xout.stride(0) if g_xout is not None else 0,
-             _ptr(g_ld), _ptr(g_blp), _ptr(g_x), g_x.stride(0), _ptr(g_p), g_p.stride(0) if g_p is not None else 0, _ptr(status)), dev)
+    _launch(name + _suffix(x), "bcast" if pb == 1 else "per-sample",
+            (_ptr(x), x.stride(0), pptr, pstride, pb, B) + layers + g_args
+            + (_ptr(g_x), g_x.stride(0), _ptr(g_p), g_p.stride(0) if g_p is not None else 0, _ptr(status)), dev)
+    return g_x, g_p
+
+
+def t_layer_inv_bwd(x, params, struct, D, g_xout, g_ld, g_blp, status=None):
+    g_x, g_p = _chain_inv_bwd("jf_t_layer_inv_bwd", x, params, D, (D, ctypes.byref(struct)), g_xout, g_ld, g_blp, status)
     if g_p is None:
-        g_p = torch.zeros((1, 0), dtype=x.dtype, device=x.device)
+        g_p = torch.zeros((1, 0), dtype=g_x.dtype, device=g_x.device)
     return g_x, g_p
 
 
 def mchain_inv_bwd(fam, x, params, layer_structs, dim, g_xout, g_ld, g_blp, status=None):
     """vector-Jacobian product of mchain(fam, 'inv', ...): -> (g_x (B, dim), g_params in the shape of `params`)."""
-    dev = require_device(x, params, g_xout, g_ld, g_blp, status)
-    x = _rowmajor(x)
-    B = x.shape[0]
-    P = 0 if params is None else params.shape[1]
-    pb = 1
-    pptr, pstride = None, 0
-    g_p = None
-    if P > 0:
-        params = _rowmajor(params)
-        pb = 1 if params.shape[0] == 1 else B
-        pptr, pstride = _ptr(params), params.stride(0)
-        g_p = torch.zeros((1, P), dtype=x.dtype, device=x.device) if pb == 1 else torch.empty((B, P), dtype=x.dtype, device=x.device)
-    if g_xout is not None:
-        g_xout = _rowmajor(g_xout)
-    g_ld = None if g_ld is None else g_ld.contiguous()
-    g_blp = None if g_blp is None else g_blp.contiguous()
-    g_x = torch.empty((B, dim), dtype=x.dtype, device=x.device)
-    n = len(layer_structs)
-    arr = (MCHAIN_LAYER_TYPES[fam] * n)(*layer_structs)
-    _launch("jf_%s_chain_inv_bwd%s" % (fam, _suffix(x)), "bcast" if pb == 1 else "per-sample",
-            (_ptr(x), x.stride(0), pptr, pstride, pb, B, n, arr, _ptr(g_xout), g_xout.stride(0) if g_xout is not None else 0, _ptr(g_ld), _ptr(g_blp),
-             _ptr(g_x), g_x.stride(0), _ptr(g_p), g_p.stride(0) if g_p is not None else 0, _ptr(status)), dev)
+    g_x, g_p = _chain_inv_bwd("jf_%s_chain_inv_bwd" % fam, x, params, dim, (len(layer_structs), mchain_layer_array(fam, layer_structs)),
+                              g_xout, g_ld, g_blp, status)
     if g_p is None:
-        g_p = torch.zeros((params.shape[0] if params is not None else 1, 0), dtype=x.dtype, device=x.device)
+        g_p = torch.zeros((params.shape[0] if params is not None else 1, 0), dtype=g_x.dtype, device=g_x.device)
     return g_x, g_p
 
 
@@ -1910,21 +1813,14 @@ MLP2_MAX_IN, MLP2_MAX_HIDDEN = 32, 128
 def mlp2(inp, w1, b1, w2, b2, out=None):
     """tanh(inp @ w1^T + b1) @ w2^T + b2 in one launch (the hidden activations stay in registers, nothing but the result reaches HBM)."""
     dev = require_device(inp, w1, b1, w2, b2, out)
-    inp, w1, w2 = _rowmajor(inp), _rowmajor(w1), _rowmajor(w2)
-    B, K1 = inp.shape
-    H, N = w1.shape[0], w2.shape[0]
-    if w1.shape[1] != K1 or w2.shape[1] != H or b1.shape[0] != H or b2.shape[0] != N:
-        raise ValueError("mlp2: inconsistent shapes")
-    if any(t.dtype != inp.dtype for t in (w1, b1, w2, b2)):
-        raise TypeError("mlp2: dtype mismatch")
+    (inp, w1, b1, _), head, B, K1, H = _mlp_head(inp, w1, b1, "mlp2", inp.dtype)
+    held2, second, N = _mlp_second(w2, b2, H, "mlp2", inp.dtype)
     if out is None:
         # rows padded to whole 128-byte lines: every 64-lane result store of the kernel then covers full, aligned HBM lines
         # (an unpadded 548-float row makes every line at a tile boundary a partial write); the pad columns are never touched
         line = 128 // inp.element_size()
         out = torch.empty((B, (N + line - 1) // line * line), dtype=inp.dtype, device=inp.device)[:, :N]
-    _launch("jf_mlp2" + _suffix(inp), "K%d_H%d_N%d" % (K1, H, N),
-            (_ptr(inp), inp.stride(0), _ptr(w1), w1.stride(0), _ptr(b1.contiguous()), _ptr(w2), w2.stride(0), _ptr(b2.contiguous()), B, K1, H, N,
-             _ptr(out), out.stride(0)), dev)
+    _launch("jf_mlp2" + _suffix(inp), "K%d_H%d_N%d" % (K1, H, N), head + second + (B, K1, H, N, _ptr(out), out.stride(0)), dev)
     return out
 
 
@@ -1959,30 +1855,15 @@ def mlp2_i8_pack(w2, b2, slices=6):
 
 def mlp2_i8(inp, w1, b1, packed, N, slices=6, out=None):
     """mlp2 in float64 with the second product as int8 digit-slice products on the matrix cores; `packed` = mlp2_i8_pack(w2, b2, slices)."""
-    seg = None
-    if isinstance(inp, SegInput):
-        if inp.in_place_ok and inp.dtype == torch.float64:
-            seg = inp                                      # read in place by jf_mlp2_i8_seg_f64
-            inp = seg.segments[0][0]
-        else:
-            inp = inp.materialize()
+    # a SegInput is read in place by jf_mlp2_i8_seg_f64 (float64 column ranges)
+    (inp, w1, b1, seg), head, B, K1, H = _mlp_head(inp, w1, b1, "mlp2_i8", torch.float64, torch.float64)
     dev = require_device(inp, w1, b1, packed, out, *(seg.tensors() if seg else []))
-    inp, w1 = _rowmajor(inp), _rowmajor(w1)
-    B, K1 = seg.shape if seg else inp.shape
-    H = w1.shape[0]
-    if w1.shape[1] != K1 or b1.shape[0] != H:
-        raise ValueError("mlp2_i8: inconsistent shapes")
-    if any(t.dtype != torch.float64 for t in (inp, w1, b1)) or packed.dtype != torch.uint8:
+    if packed.dtype != torch.uint8:
         raise TypeError("mlp2_i8: float64 inputs and a uint8 packed image expected")
     if packed.numel() != int(lib().jf_mlp2_i8_packed_bytes(N, slices)):
         raise ValueError("mlp2_i8: the packed image does not belong to N = %d, slices = %d" % (N, slices))
     if out is None:
         out = torch.empty((B, (N + 15) // 16 * 16), dtype=inp.dtype, device=inp.device)[:, :N]      # rows of whole 128-byte lines (see mlp2)
-    if seg is not None:
-        arr = seg.c_array()
-        _launch("jf_mlp2_i8_seg_f64", "K%d_H%d_N%d_x%d" % (K1, H, N, slices),
-                (arr, len(seg.segments), _ptr(w1), w1.stride(0), _ptr(b1.contiguous()), _ptr(packed), B, K1, H, N, slices, _ptr(out), out.stride(0)), dev)
-        return out
-    _launch("jf_mlp2_i8_f64", "K%d_H%d_N%d_x%d" % (K1, H, N, slices),
-            (_ptr(inp), inp.stride(0), _ptr(w1), w1.stride(0), _ptr(b1.contiguous()), _ptr(packed), B, K1, H, N, slices, _ptr(out), out.stride(0)), dev)
+    _launch("jf_mlp2_i8_seg_f64" if seg else "jf_mlp2_i8_f64", "K%d_H%d_N%d_x%d" % (K1, H, N, slices),
+            head + (_ptr(packed), B, K1, H, N, slices, _ptr(out), out.stride(0)), dev)
     return out

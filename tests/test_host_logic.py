@@ -36,6 +36,46 @@ def test_library_exports_every_declared_symbol():
     assert lib.jf_abi_version() >= 1
 
 
+def test_argtypes_match_the_header_prototypes():
+    """every prototype of include/jammy_hip.h, macros expanded by the preprocessor, against the argtypes the binding declares for it: the same
+    number of arguments and the same kind in every position -- pointer, pointer to a named struct, int32, int64, double (a void* in the
+    table may stand for any pointer) -- and no entry point but jf_abi_version missing from the table"""
+    import shutil
+    import subprocess
+    from jammy_flows_amd import _hip
+    clang = "/opt/rocm/lib/llvm/bin/clang" if os.path.exists("/opt/rocm/lib/llvm/bin/clang") else shutil.which("clang")
+    if not clang:
+        pytest.skip("clang not available")
+    text = subprocess.run([clang, "-E", "-P", "-x", "c", os.path.join(ROOT, "include", "jammy_hip.h")], check=True, capture_output=True,
+                          text=True).stdout
+    protos = re.findall(r"\b(?:int|int32_t|int64_t)\s+(jf_\w+)\s*\(([^()]*)\)\s*;", re.sub(r"\s+", " ", text))
+
+    def header_kind(arg):
+        if "*" in arg:
+            m = re.match(r"(?:const )?(?:struct )?(jf_\w+)\s*\*", arg)
+            return "pointer to " + m.group(1) if m else "pointer"
+        words = [w for w in arg.split() if w != "const"]
+        return {"int": "int32", "int32_t": "int32", "int64_t": "int64", "double": "double"}[words[0]]
+
+    def table_kind(t):
+        if t is ctypes.c_void_p:
+            return "pointer"
+        if isinstance(getattr(t, "_type_", None), type):                     # ctypes.POINTER(struct or scalar type)
+            return "pointer to " + t._type_.__name__ if issubclass(t._type_, ctypes.Structure) else "pointer"
+        return {ctypes.c_int32: "int32", ctypes.c_int: "int32", ctypes.c_int64: "int64", ctypes.c_double: "double"}[t]
+
+    header = {name: [header_kind(a.strip()) for a in args.split(",") if a.strip() not in ("", "void")] for name, args in protos}
+    table = {base + suf: [table_kind(t) for t in argtypes] for base, argtypes in _hip._SIGNATURES.items() for suf in ("_f32", "_f64")}
+    table.update({name: [table_kind(t) for t in argtypes] for name, (argtypes, _) in _hip._SIGNATURES_SINGLE.items()})
+    assert len(header) == len(protos) and len(header) > 200                  # (no prototype seen twice; the parser has not gone blind)
+    assert set(header) - {"jf_abi_version"} == set(table), (set(header) - {"jf_abi_version"}) ^ set(table)
+    for name, kinds in sorted(table.items()):
+        want = header[name]
+        assert len(kinds) == len(want), (name, want, kinds)
+        for i, (k, w) in enumerate(zip(kinds, want)):
+            assert k == w or (k == "pointer" and w.startswith("pointer")), "%s: argument %d is %s in the header, %s in the table" % (name, i, w, k)
+
+
 def test_gf_layer_struct_matches_header():
     from jammy_flows_amd import _hip
     # 12 int32 + 4 double, no padding surprises: sizeof must be 12*4 + 4*8
