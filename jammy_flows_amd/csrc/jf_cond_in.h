@@ -86,6 +86,42 @@ __device__ __forceinline__ bool cond_in_any_embed(const CondIn& a) {
     return e;
 }
 
+// Row-wise staging (a thread owns a whole input row and walks its columns in order): the thread's pointer to the current column's element.
+// Segment index, columns left in the segment and its kind are wave-uniform (kernel arguments), so the walk is scalar code; only the pointer
+// is per lane, set once per segment and bumped per column.  The plain (in, in_stride) matrix is one segment of kind 0.
+struct CondWalk {
+    const float* p; int seg, left, kind;
+    __device__ __forceinline__ CondWalk(const float* in, int64_t in_stride, int K1, int64_t row) : p(in + row * in_stride), seg(0), left(K1), kind(0) {}
+    __device__ __forceinline__ CondWalk() : p(nullptr), seg(-1), left(0), kind(0) {}
+    // call before reading column c (c below the row's width): moves to the segment that holds it
+    __device__ __forceinline__ void enter(const CondIn& a, int64_t row) {
+        // (uniform; a plain segment may be empty.  The host checks that the widths add up to K1 -- cond_in_make -- so a column below K1
+        // always has its segment; a bound on seg in this condition makes hipcc unroll the walk eightfold and spill 170 scalar registers)
+        while (left == 0) {
+            ++seg;
+            // the segment's fields by a chain of scalar selects: an index the compiler does not know would move the kernel's whole
+            // argument block to private memory
+            const void* src = a.s[0].src; int64_t stride = a.s[0].stride; int n_in = a.s[0].n_in;
+            kind = a.s[0].kind;
+#pragma unroll
+            for (int i = 1; i < JF_COND_IN_MAX; ++i)
+                if (seg == i) { src = a.s[i].src; stride = a.s[i].stride; n_in = a.s[i].n_in; kind = a.s[i].kind; }
+            left = kind == 0 ? n_in : kind + 1;
+            p = static_cast<const float*>(src) + row * stride;
+        }
+    }
+    __device__ __forceinline__ void next() { ++p; --left; }
+};
+// the columns of an embedded segment from its angles (va = r[0], vb = r[kind - 1]), bit for bit cond_in_finish<float, true>: S1 (cos, sin),
+// S2 (sin th cos ph, sin th sin ph, cos th) with th = safe_angle_pi(r[0]); each sine / cosine once per row
+__device__ __forceinline__ void cond_in_embed(int kind, float va, float vb, float* out) {
+    using TR = CondTrig<true>;
+    const float th = kind == 2 ? safe_angle_pi(va) : va;
+    const float s1 = TR::sin(th), c1 = TR::cos(th);
+    if (kind == 1) { out[0] = c1; out[1] = s1; return; }
+    out[0] = s1 * TR::cos(vb); out[1] = s1 * TR::sin(vb); out[2] = c1;
+}
+
 // host: segments -> CondIn; their widths must add up to the MLP's input width K1
 static inline int cond_in_make(const jf_cond_segment* segs, int32_t n, int32_t K1, CondIn& out) {
     if (!segs || n < 1 || n > JF_COND_IN_MAX) return n > JF_COND_IN_MAX ? JF_ERR_UNSUPPORTED : JF_ERR_BADARG;

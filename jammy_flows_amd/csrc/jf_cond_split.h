@@ -94,6 +94,17 @@ __device__ __forceinline__ void cs_split16(float v0, float v1, unsigned& hi, uns
     hi = __builtin_bit_cast(unsigned, h);
     lo = __builtin_bit_cast(unsigned, l);
 }
+// the same values for operands that are NOT a product the compiler could fold into the residual (cs_split16(h * scale, ...) becomes
+// fma(h, scale, -hi) reading the f16 half directly): the residual written as fma(hi, m, v) with m = -1 behind an empty asm.  A multiplier
+// the compiler cannot see keeps the fma (v_fma_mix_f32: 4 instructions per pair); a visible -1 turns it into two v_cvt_f32_f16 and two v_sub
+__device__ __forceinline__ void cs_split16_plain(float v0, float v1, unsigned& hi, unsigned& lo) {
+    float m = -1.0f;
+    asm("" : "+s"(m));
+    const f16x2 h = __builtin_convertvector(f32x2{v0, v1}, f16x2);
+    const f16x2 l = __builtin_convertvector(f32x2{__builtin_fmaf((float)h[0], m, v0), __builtin_fmaf((float)h[1], m, v1)}, f16x2);
+    hi = __builtin_bit_cast(unsigned, h);
+    lo = __builtin_bit_cast(unsigned, l);
+}
 constexpr int CS_ROWS1 = 64;                       // rows per workgroup and row group (4 waves x 16); a wave carries RG row groups
 constexpr int CS_HMAX = 128, CS_K1MAX = 28;
 
@@ -147,92 +158,129 @@ __device__ __forceinline__ void cs_dma_chunk(__amdgpu_buffer_rsrc_t rsrc, unsign
 }
 
 // ---------------------------------------------------------------------------------------------------------- phase 1
-// h^T = tanh(W1 x^T + b1) for the wave's RG x 16 rows (exact f32 MFMA; rows past B replicate row B-1), returned as MFMA B operands: three
-// bf16 pieces per value, k-slot i of lane group q in k-step s = hidden unit 16 (2 s + i / 4) + 4 q + i % 4.  Xs: LDS scratch of
-// (CS_ROWS1 RG + CS_HMAX) (k1p + 1) + CS_HMAX floats.  STORE_H: the f32 activations also go to h_out (B, H) -- the adjoint's weight-gradient
-// product reads them.  Ends with every wave past the barrier that follows the staging, NOT past one after the MFMA reads: the caller's next
-// barrier covers those.
+// h^T = tanh(W1 x^T + b1) for the wave's RG x 16 rows (exact f32 MFMA; rows past B replicate row B-1), returned as MFMA B operands: NP
+// pieces per value (three bf16, or two f16 of h 2^14), k-slot i of lane group q in k-step s = hidden unit 16 (2 s + i / 4) + 4 q + i % 4.
+// Xs: LDS scratch of (CS_ROWS1 RG + CS_HMAX) (k1p + 1) + CS_HMAX floats.  STORE_H: the f32 activations also go to h_out (B, H) -- the
+// adjoint's weight-gradient product reads them.  Ends with every wave past the barrier that follows the staging, NOT past one after the
+// MFMA reads: the caller's next barrier covers those.
 template <int RG, bool STORE_H, int NP = CS_NP>
 __device__ __forceinline__ void cs_hidden(const float* __restrict__ in, int64_t in_stride, const float* __restrict__ W1, int64_t w1s,
                                           const float* __restrict__ b1, int K1, int H, int64_t row0, int64_t last, float* Xs,
                                           bf16x8 (&hB)[RG][CS_KSTEPS][NP], float* __restrict__ h_out, int64_t hs, const CondIn* cin = nullptr) {
     using MF = Mfma16<float>;
     constexpr int CS_ROWS = CS_ROWS1 * RG;
-    constexpr int MT = 16, KS = 4, NREG = 4, JH = CS_HMAX / MT;
+    constexpr int MT = 16, KS = 4, JH = CS_HMAX / MT;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, lq = lane >> 4;
     const int k1p = (K1 + KS - 1) / KS * KS, ldk = k1p + 1;
     float* W1s = Xs + CS_ROWS * ldk;
     float* b1s = W1s + CS_HMAX * ldk;
-    {
-        const int nx = CS_ROWS * k1p, nw = CS_HMAX * k1p;
+    // f16 pairs: W1 and b1 are staged times 2 log2(e), so the matrix product below IS the v_exp_f32 argument of tanh
+    constexpr float PRE = NP == 2 ? 2.8853900817779268f : 1.0f;
+    // Staging, one row per thread: thread t < CS_ROWS owns input row t of the tile, the next CS_HMAX threads one hidden unit (a row of W1 and
+    // its bias) each.  A thread walks its row's columns in order, eight per turn (one turn up to K1 = 8): no index division, no per-element
+    // segment search, and the segment bookkeeping is scalar (CondWalk).  Every branch is wave-uniform (CS_ROWS is a multiple of 64: a wave
+    // stages rows or hidden units, never both); all the global loads of a turn, and the angles of the embedded segments before the first
+    // turn, are issued before the first LDS write (a load waited for inside a branch is a round trip of its own: jf_cond_in.h).
+    constexpr int CG = 8;
+    const int wv = __builtin_amdgcn_readfirstlane(wave);
+    if (wv * 64 < CS_ROWS) {
+        const int64_t avail = last - row0;
+        const int64_t row = row0 + (tid <= avail ? tid : avail);   // rows past B replicate row B-1
+        float ea[JF_COND_IN_MAX], eb[JF_COND_IN_MAX];
         if (cin) {
-            // segments (jf_cond_in.h): locate, then every load of the batch, then the embedding arithmetic -- straight-line, one wait
-            const bool any_embed = cond_in_any_embed(*cin);
-            for (int base = 0; base < nx; base += 4 * 256) {
-                CondLoc<float> loc[4]; float va[4], vb[4]; int o[4]; bool keep[4];
 #pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int idx = base + u * 256 + tid;
-                    const int r = idx / k1p, c = idx - r * k1p;
-                    const int64_t gr = row0 + r;
-                    loc[u] = cond_in_locate<float>(*cin, gr <= last ? gr : last, c < K1 ? c : 0);
-                    keep[u] = c < K1;
-                    o[u] = idx < nx ? r * ldk + c : -1;
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) { va[u] = *loc[u].pa; vb[u] = *loc[u].pb; }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const float t = cond_in_finish<float, true>(loc[u], va[u], vb[u], any_embed);
-                    if (o[u] >= 0) Xs[o[u]] = keep[u] ? t : 0.f;
+            for (int i = 0; i < JF_COND_IN_MAX; ++i) {
+                if (i < cin->n && cin->s[i].kind != 0) {
+                    const float* r = static_cast<const float*>(cin->s[i].src) + row * cin->s[i].stride;
+                    ea[i] = r[0]; eb[i] = r[cin->s[i].kind - 1];
                 }
             }
-        } else
-        for (int base = 0; base < nx; base += 4 * 256) {
-            float v[4]; int o[4];
+        }
+        float* xr = Xs + tid * ldk;
+        CondWalk w = cin ? CondWalk() : CondWalk(in, in_stride, K1, row);
+        for (int c0 = 0; c0 < k1p; c0 += CG) {
+            float v[CG]; bool plain[CG];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int idx = base + u * 256 + tid;
-                const int r = idx / k1p, c = idx - r * k1p;
-                const int64_t gr = row0 + r;
-                const float t = in[(gr <= last ? gr : last) * in_stride + (c < K1 ? c : 0)];
-                v[u] = c < K1 ? t : 0.f;
-                o[u] = idx < nx ? r * ldk + c : -1;
+            for (int u = 0; u < CG; ++u) {
+                plain[u] = false;
+                if (c0 + u < K1) {
+                    if (cin) w.enter(*cin, row);
+                    plain[u] = w.kind == 0;
+                    if (plain[u]) v[u] = *w.p;
+                    w.next();
+                }
             }
 #pragma unroll
-            for (int u = 0; u < 4; ++u) if (o[u] >= 0) Xs[o[u]] = v[u];
-        }
-        for (int base = 0; base < nw; base += 4 * 256) {
-            float v[4]; int o[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int idx = base + u * 256 + tid;
-                const int r = idx / k1p, c = idx - r * k1p;
-                const float t = W1[(int64_t)(r < H ? r : H - 1) * w1s + (c < K1 ? c : 0)];
-                v[u] = (r < H && c < K1) ? t : 0.f;
-                o[u] = idx < nw ? r * ldk + c : -1;
+            for (int u = 0; u < CG; ++u) {
+                if (plain[u]) xr[c0 + u] = v[u];
+                else if (c0 + u >= K1 && c0 + u < k1p) xr[c0 + u] = 0.f;
             }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) if (o[u] >= 0) W1s[o[u]] = v[u];
         }
-        if (tid < CS_HMAX) b1s[tid] = tid < H ? b1[tid < H ? tid : 0] : 0.f;
+        if (cin) {
+            int off = 0;
+#pragma unroll
+            for (int i = 0; i < JF_COND_IN_MAX; ++i) {
+                if (i < cin->n) {
+                    const int kind = cin->s[i].kind;
+                    if (kind != 0) {
+                        // the angles become visible to the compiler only here, behind the plain columns' loads and writes: it otherwise
+                        // starts the embedding's arithmetic, and waits for the angles, right behind their loads
+                        asm volatile("" : "+v"(ea[i]), "+v"(eb[i]) : : "memory");
+                        cond_in_embed(kind, ea[i], eb[i], xr + off);
+                    }
+                    off += kind == 0 ? cin->s[i].n_in : kind + 1;
+                }
+            }
+        }
+    } else if (wv * 64 < CS_ROWS + CS_HMAX) {
+        const int hu = tid - CS_ROWS, hc = hu < H ? hu : H - 1;
+        const float sc = hu < H ? PRE : 0.f;                        // units past H: zero weights, zero bias
+        const float* wr = W1 + (int64_t)hc * w1s;
+        const float b = b1[hc];
+        float* ws = W1s + hu * ldk;
+        for (int c0 = 0; c0 < k1p; c0 += CG) {
+            float v[CG];
+#pragma unroll
+            for (int u = 0; u < CG; ++u)
+                if (c0 + u < K1) v[u] = wr[c0 + u];
+#pragma unroll
+            for (int u = 0; u < CG; ++u) {
+                if (c0 + u < K1) ws[c0 + u] = v[u] * sc;
+                else if (c0 + u < k1p) ws[c0 + u] = 0.f;
+            }
+        }
+        b1s[hu] = b * sc;
     }
     __syncthreads();
+    // the accumulators start from the bias: register r of tile j = hidden unit 16 j + 4 lq + r.  k-steps unrolled behind uniform guards
+    // (K1 <= 28: at most 7; the first always runs, so its MFMAs take the bias registers as C and no copy is made); a step's W1 fragment
+    // feeds every row group
+    typename MF::Acc acc[RG][JH];
+#pragma unroll
+    for (int j = 0; j < JH; ++j) {
+        const f32x4 bias = *reinterpret_cast<const f32x4*>(b1s + j * MT + 4 * lq);
+#pragma unroll
+        for (int g = 0; g < RG; ++g) acc[g][j] = bias;
+    }
+#pragma unroll
+    for (int s = 0; s < CS_K1MAX / KS; ++s) {
+        if (s == 0 || s * KS < k1p) {                              // uniform
+            const int kk = s * KS + lq;
+            float xb[RG], wa[JH];
+#pragma unroll
+            for (int g = 0; g < RG; ++g) xb[g] = Xs[((wave * RG + g) * MT + li) * ldk + kk];
+#pragma unroll
+            for (int j = 0; j < JH; ++j) wa[j] = W1s[(j * MT + li) * ldk + kk];
+#pragma unroll
+            for (int j = 0; j < JH; ++j)
+#pragma unroll
+                for (int g = 0; g < RG; ++g) acc[g][j] = MF::mma(wa[j], xb[g], acc[g][j]);
+        }
+    }
 #pragma unroll
     for (int g = 0; g < RG; ++g) {
-        typename MF::Acc acc[JH];
-#pragma unroll
-        for (int j = 0; j < JH; ++j)
-#pragma unroll
-            for (int r = 0; r < NREG; ++r) acc[j][r] = 0.f;
-        for (int s = 0; s < k1p / KS; ++s) {
-            const int kk = s * KS + lq;
-            const float xb = Xs[((wave * RG + g) * MT + li) * ldk + kk];
-#pragma unroll
-            for (int j = 0; j < JH; ++j) acc[j] = MF::mma(W1s[(j * MT + li) * ldk + kk], xb, acc[j]);
-        }
-        // acc[j][r] = pre-activation of hidden unit 16 j + 4 lq + r for row li: k-slot i of k-step s <-> (j = 2 s + i / 4, r = i % 4)
+        // acc[g][j][r] = pre-activation of hidden unit 16 j + 4 lq + r for row li: k-slot i of k-step s <-> (j = 2 s + i / 4, r = i % 4)
 #pragma unroll
         for (int s = 0; s < CS_KSTEPS; ++s) {
             // split by truncation, two values at a time (and / sub / and / sub + one v_perm_b32 per packed pair; exact as well: 24 significant
@@ -242,15 +290,18 @@ __device__ __forceinline__ void cs_hidden(const float* __restrict__ in, int64_t 
 #pragma unroll
             for (int i = 0; i < 8; i += 2) {
                 const int j = 2 * s + (i >> 2), r = i & 3;
-                const float h0 = M<float>::tanh_fast(acc[j][r] + b1s[j * MT + 4 * lq + r]);
-                const float h1 = M<float>::tanh_fast(acc[j][r + 1] + b1s[j * MT + 4 * lq + r + 1]);
-                if constexpr (STORE_H) { acc[j][r] = h0; acc[j][r + 1] = h1; }
                 if constexpr (NP == 2) {
+                    // h 2^14 = 2^14 (1 - 2 / (e^{2a} + 1)) in one fma behind the reciprocal; the split takes it as it is
+                    const float t0 = fmaf(-2.0f * CS_H_SCALE, __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(acc[g][j][r]) + 1.0f), CS_H_SCALE);
+                    const float t1 = fmaf(-2.0f * CS_H_SCALE, __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(acc[g][j][r + 1]) + 1.0f), CS_H_SCALE);
+                    if constexpr (STORE_H) { acc[g][j][r] = t0 * (1.0f / CS_H_SCALE); acc[g][j][r + 1] = t1 * (1.0f / CS_H_SCALE); }   // exact
                     unsigned ph, pl;
-                    cs_split16(h0 * CS_H_SCALE, h1 * CS_H_SCALE, ph, pl);
+                    cs_split16_plain(t0, t1, ph, pl);
                     q0[i >> 1] = ph; q1[i >> 1] = pl;
                     continue;
                 }
+                const float h0 = M<float>::tanh_fast(acc[g][j][r]), h1 = M<float>::tanh_fast(acc[g][j][r + 1]);
+                if constexpr (STORE_H) { acc[g][j][r] = h0; acc[g][j][r + 1] = h1; }
                 const unsigned a0 = __builtin_bit_cast(unsigned, h0), a1 = __builtin_bit_cast(unsigned, h1);
                 const float r0 = h0 - __builtin_bit_cast(float, a0 & 0xffff0000u), r1 = h1 - __builtin_bit_cast(float, a1 & 0xffff0000u);
                 const unsigned c0 = __builtin_bit_cast(unsigned, r0), c1 = __builtin_bit_cast(unsigned, r1);
@@ -268,7 +319,7 @@ __device__ __forceinline__ void cs_hidden(const float* __restrict__ in, int64_t 
 #pragma unroll
                 for (int j = 0; j < JH; ++j) {
                     const int c = j * MT + 4 * lq;                 // hidden units c .. c + 3 (H is a multiple of 4 on this path)
-                    if (c < H) *reinterpret_cast<f32x4*>(h_out + r * hs + c) = acc[j];
+                    if (c < H) *reinterpret_cast<f32x4*>(h_out + r * hs + c) = acc[g][j];
                 }
             }
         }
