@@ -881,9 +881,10 @@ def gf_chain(direction, x, log_det, params, layer_array, n_layers, D, x_out=None
     return x_out, ld_out
 
 
-def gf_chain_inv_cot(x, params, layer_array, n_layers, D, cot):
+def gf_chain_inv_cot(x, params, layer_array, n_layers, D, cot, want_x_out=False):
     """J^{-T} cot for the Jacobian J of gf_chain('inv', x, ...) at x (the co-vector carried through the layers: jf_gf_chain_inv_cot); None for layers
-    with the general options (the caller then solves with a dense Jacobian)"""
+    with the general options (the caller then solves with a dense Jacobian).  want_x_out: -> (J^{-T} cot, x_out), the chain's output with it (a
+    block cut into several launches carries both from launch to launch)"""
     dev = require_device(x, params, cot)
     x, cot = _rowmajor(x), _rowmajor(cot)
     B = x.shape[0]
@@ -891,14 +892,16 @@ def gf_chain_inv_cot(x, params, layer_array, n_layers, D, cot):
         raise ValueError("gf_chain_inv_cot: inconsistent shapes / dtypes")
     params, pptr, pstride, pb = _param_rows(params, B, None, "gf_chain_inv_cot")
     out = torch.empty((B, D), dtype=x.dtype, device=x.device)
-    if B == 0:
-        return out
     x_out = torch.empty((B, D), dtype=x.dtype, device=x.device)
+    if B == 0:
+        return (out, x_out) if want_x_out else out
     ld_out = torch.empty((B,), dtype=x.dtype, device=x.device)
     ok = _launch("jf_gf_chain_inv_cot" + _suffix(x), "bcast" if pb == 1 else "per-sample",
                  (_ptr(x), x.stride(0), pptr, pstride, pb, B, D, n_layers, layer_array, _ptr(cot), cot.stride(0), _ptr(out), out.stride(0),
                   _ptr(x_out), x_out.stride(0), _ptr(ld_out)), dev, unsupported_ok=True)
-    return out if ok is not False else None
+    if ok is False:
+        return None
+    return (out, x_out) if want_x_out else out
 
 
 def gf_chain_inv_bwd(x, params, layer_array, n_layers, D, g_xout, g_ld, g_blp, status=None):

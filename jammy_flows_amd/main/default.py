@@ -1296,7 +1296,8 @@ class pdf(nn.Module):
         Same launches as the inference path, wrapped in autograd Functions whose backward is a HIP launch (g chains, manifold chains) or
         rocBLAS GEMMs (dense layers) -- see jammy_flows_amd/autograd.py.
         collect (optional list): receives one dict per sub-pdf -- its target columns (a, b), its base coordinates y WITH their graph, and for
-        pure g chains `cot`: v -> J_block^-T v, the co-vector carried through the block's layers by one launch (jf_gf_chain_inv_cot) -- what
+        pure g chains `cot`: v -> J_block^-T v, the co-vector carried through the block's layers by one launch per launch group
+        (jf_gf_chain_inv_cot; a wide block such as e33 "gg" is several groups, it used to fall back to the dense D x D solve) -- what
         the implicit-function adjoint of sampling needs (_differentiable_sample)."""
         log_det0 = None
         if force_embedding_coordinates:          # the chart changes ahead of the block loop, with a graph (autograd.SphereEmbeddingFn)
@@ -1450,7 +1451,8 @@ class pdf(nn.Module):
             bases.append(out)
             if collect is not None:
                 cot = None
-                if kind == "e" and gfl.chain_supported(layers) and not only_last and amort is None:
+                if (kind == "e" and all(type(l) is gfl.gf_block for l in layers) and layers[0].dimension <= _hip.GF_MAX_DIM and not only_last
+                        and amort is None):
                     def cot(v, si=si, layers=layers, tgt=tgt.detach(), inp=None if inp is None else inp.detach(), mlp=mlp):
                         with torch.no_grad():
                             if mlp is not None:
@@ -1458,8 +1460,18 @@ class pdf(nn.Module):
                                 params = params[:, :-1] if self._poisson_column(si) else params
                             else:
                                 params = gfl.chain_permanent_row(layers, tgt)
-                            return _hip.gf_chain_inv_cot(tgt, params, _hip.gf_layer_array([l.c_struct() for l in layers]), len(layers),
-                                                         layers[0].dimension, v)
+                            # one launch for a block that runs as one; a wide block cut into several (_layer_groups: a CU's LDS) carries the
+                            # co-vector and the coordinates from launch to launch, last group first, parameters sliced tail-first like the block's
+                            cur, c1 = tgt, params.shape[1]
+                            for grp in reversed(_layer_groups(layers)):
+                                n = sum(l.total_param_num for l in grp)
+                                res = _hip.gf_chain_inv_cot(cur, params[:, c1 - n:c1], _hip.gf_layer_array([l.c_struct() for l in grp]), len(grp),
+                                                            grp[0].dimension, v, want_x_out=True)
+                                if res is None:
+                                    return None
+                                v, cur = res
+                                c1 -= n
+                            return v
                 collect.append({"a": a, "b": b, "y": out, "cot": cot, "coupled": mlp is not None and len(embeds) > 0})
             emb = block[-1]._embedding_conditional_return(tgt.detach()) if not tgt.requires_grad else autograd.embed(tgt, kind, layers[-1])
             embeds.append(emb)

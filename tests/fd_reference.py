@@ -13,6 +13,7 @@ import numpy as np
 
 REL_STEP = 1e-4          # float64: D(h/2) rounding ~1e-16 |f| / h ~ 1e-12 |f|, extrapolated truncation ~h^4 |f^(5)|: far below the 1e-6 bars; a kink
                          # (spline knot, clamp) is met by few rows at this step
+MAX_SKIP = 0.05          # of a fuzz module's checks may be skipped for FD noise (a kink within the step); no case may lose all of its checks
 
 
 def directional_fd(f, x0, v, rel_step=REL_STEP):
@@ -87,3 +88,76 @@ def chain_inverse(specs, x, params, want_base_logp=True):
         x, ld, _ = ogf.inverse(s, x, ld, params[:, lo:hi])
     blp = np.sum(-0.5 * x * x - 0.5 * np.log(2.0 * np.pi), axis=1) if want_base_logp else None
     return x, ld, blp
+
+
+
+def covector_identity(f, x, lam, v, u):
+    """backward-error check of a claimed lam = J^-T v for the Jacobian J = df/dx of the per-row map f at x, along the directions u (one per row):
+    lam . (J u) = v . u for every u, with J u one directional_fd of f.  No dense solve enters, so the check does not feel the conditioning of J.
+    Returns per row (lam . J u, v . u, noise = sum_i |lam_i| spread_i, scale = sum_i |lam_i (J u)_i|)."""
+    Ju, sp = directional_fd(f, x, u)
+    return (lam * Ju).sum(axis=1), (v * u).sum(axis=1), (np.abs(lam) * sp).sum(axis=1), np.abs(lam * Ju).sum(axis=1)
+
+
+def sample_loss_rows(oracle, z, cond, w, embedding=False):
+    """the rows of loss = mean <w, x> + 0.1 mean log_prob over the samples x = oracle.sample_from_base(z, cond) (the loss of the sampling-gradient
+    fixtures): their sum is the loss"""
+    x, logp = oracle.sample_from_base(z, cond, force_embedding_coordinates=embedding)[:2]
+    return ((np.asarray(x, dtype=np.float64) * w).sum(axis=1) + 0.1 * logp) / z.shape[0]
+
+
+def new_totals():
+    """a fuzz module's running sums: every Tally of the module adds to them, skip_cap_met() judges them when the module is done"""
+    return {"checks": 0, "skipped": 0, "noise": 0.0, "worst": 0.0}
+
+
+def skip_cap_met(totals):
+    return totals["skipped"] <= MAX_SKIP * totals["checks"]
+
+
+class Tally:
+    """checks, skips, worst error and FD noise (spread) relative to the bar's scale.  A block whose derivative vanishes identically (the weight of
+    a one-component mixture, a reflection in one dimension, the widths of a one-bin spline) has no scale of its own: every scale is floored at
+    ZERO_FLOOR times the largest scale of the case, so that the kernel's rounding residue there is measured against the case's gradients."""
+
+    ZERO_FLOOR = 1e-3
+
+    def __init__(self, what, totals):
+        self.totals = totals
+        self.what, self.n, self.skipped, self.worst, self.noise, self.fail, self.pending = what, 0, [], 0.0, 0.0, [], []
+
+    def check(self, name, got, fd, spread, scale, bar, skip_bar=None):
+        """skip_bar (default: bar): a check whose h and h/2 estimates differ by more than skip_bar times its scale is skipped"""
+        got, fd, spread = np.atleast_1d(got), np.atleast_1d(fd), np.atleast_1d(spread)
+        self.pending.append((name, got, fd, spread, np.broadcast_to(np.asarray(scale, dtype=np.float64), fd.shape), bar,
+                             bar if skip_bar is None else skip_bar))
+
+    def _evaluate(self):
+        top = max([float(np.max(sc[np.isfinite(sc)])) for _, _, _, _, sc, _, _ in self.pending if np.isfinite(sc).any()] or [0.0])
+        for name, got, fd, spread, scale, bar, skip_bar in self.pending:
+            scale = np.maximum(scale, max(self.ZERO_FLOOR * top, 1e-300))
+            fin = np.isfinite(fd) & np.isfinite(spread)
+            noisy = fin & (spread > skip_bar * scale)
+            use = fin & ~noisy
+            self.n += int(fin.sum())
+            if noisy.any():
+                self.skipped.append((name, int(noisy.sum())))
+            if use.any():
+                err = np.abs(got[use] - fd[use]) / scale[use]
+                err = np.where(np.isfinite(err), err, np.inf)
+                self.noise = max(self.noise, float(np.max(spread[use] / scale[use])))
+                self.worst = max(self.worst, float(np.max(err)))
+                if not np.all(err <= bar):
+                    self.fail.append("%s: %d of %d off, worst %.3g (bar %.0e)" % (name, int((~(err <= bar)).sum()), int(use.sum()), float(np.max(err)), bar))
+
+    def finish(self):
+        self._evaluate()
+        n_skip = sum(k for _, k in self.skipped)
+        print("%s: %d checks, %d skipped %s, worst %.3g of scale, FD noise %.3g of scale" % (self.what, self.n, n_skip, self.skipped, self.worst,
+                                                                                             self.noise))
+        self.totals["checks"] += self.n
+        self.totals["skipped"] += n_skip
+        self.totals["noise"] = max(self.totals["noise"], self.noise)
+        self.totals["worst"] = max(self.totals.get("worst", 0.0), self.worst)
+        assert not self.fail, "%s: %s" % (self.what, "; ".join(self.fail))
+        assert self.n > 0 and n_skip < self.n, "%s: every check skipped" % self.what

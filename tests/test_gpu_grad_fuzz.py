@@ -28,12 +28,12 @@ pytestmark = pytest.mark.gpu
 BAR64 = 1e-6             # float64: of each block's / tensor's FD scale
 BAR64_INORMAL = 2e-4     # float64 g chains with an inverse-normal layer (see test_g_chain_adjoint_vs_finite_differences)
 BAR32 = 2e-3             # float32: of each tensor's largest gradient entry
-MAX_SKIP = 0.05
+MAX_SKIP = fdr.MAX_SKIP      # 0.05
 DIMS = list(range(1, 10)) + [15, 16, 17, 31, 32, 33, 46, 47, 48, 63, 64]
 N_CHAIN_CASES = 72
 
 
-TOTALS = {"checks": 0, "skipped": 0, "noise": 0.0}
+TOTALS = fdr.new_totals()
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -44,52 +44,6 @@ def _wall_time_and_skips():
     print("\ntest_gpu_grad_fuzz: wall time %.1f s, %d checks, %d skipped, FD noise floor (h vs h/2 spread) %.3g of the bar's scale"
           % (time.time() - t0, TOTALS["checks"], TOTALS["skipped"], TOTALS["noise"]))
     assert TOTALS["skipped"] <= MAX_SKIP * TOTALS["checks"], TOTALS
-
-
-class Tally:
-    """checks, skips, worst error and FD noise (spread) relative to the bar's scale.  A block whose derivative vanishes identically (the weight of
-    a one-component mixture, a reflection in one dimension, the widths of a one-bin spline) has no scale of its own: every scale is floored at
-    ZERO_FLOOR times the largest scale of the case, so that the kernel's rounding residue there is measured against the case's gradients."""
-
-    ZERO_FLOOR = 1e-3
-
-    def __init__(self, what):
-        self.what, self.n, self.skipped, self.worst, self.noise, self.fail, self.pending = what, 0, [], 0.0, 0.0, [], []
-
-    def check(self, name, got, fd, spread, scale, bar, skip_bar=None):
-        """skip_bar (default: bar): a check whose h and h/2 estimates differ by more than skip_bar times its scale is skipped"""
-        got, fd, spread = np.atleast_1d(got), np.atleast_1d(fd), np.atleast_1d(spread)
-        self.pending.append((name, got, fd, spread, np.broadcast_to(np.asarray(scale, dtype=np.float64), fd.shape), bar,
-                             bar if skip_bar is None else skip_bar))
-
-    def _evaluate(self):
-        top = max([float(np.max(sc[np.isfinite(sc)])) for _, _, _, _, sc, _, _ in self.pending if np.isfinite(sc).any()] or [0.0])
-        for name, got, fd, spread, scale, bar, skip_bar in self.pending:
-            scale = np.maximum(scale, max(self.ZERO_FLOOR * top, 1e-300))
-            fin = np.isfinite(fd) & np.isfinite(spread)
-            noisy = fin & (spread > skip_bar * scale)
-            use = fin & ~noisy
-            self.n += int(fin.sum())
-            if noisy.any():
-                self.skipped.append((name, int(noisy.sum())))
-            if use.any():
-                err = np.abs(got[use] - fd[use]) / scale[use]
-                err = np.where(np.isfinite(err), err, np.inf)
-                self.noise = max(self.noise, float(np.max(spread[use] / scale[use])))
-                self.worst = max(self.worst, float(np.max(err)))
-                if not np.all(err <= bar):
-                    self.fail.append("%s: %d of %d off, worst %.3g (bar %.0e)" % (name, int((~(err <= bar)).sum()), int(use.sum()), float(np.max(err)), bar))
-
-    def finish(self):
-        self._evaluate()
-        n_skip = sum(k for _, k in self.skipped)
-        print("%s: %d checks, %d skipped %s, worst %.3g of scale, FD noise %.3g of scale" % (self.what, self.n, n_skip, self.skipped, self.worst,
-                                                                                             self.noise))
-        TOTALS["checks"] += self.n
-        TOTALS["skipped"] += n_skip
-        TOTALS["noise"] = max(TOTALS["noise"], self.noise)
-        assert not self.fail, "%s: %s" % (self.what, "; ".join(self.fail))
-        assert self.n > 0 and n_skip < self.n, "%s: every check skipped" % self.what
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------------
@@ -140,7 +94,7 @@ def test_g_chain_adjoint_vs_finite_differences(seed):
     # the FD can decide is judged at BAR64 either way.
     bar = BAR64 if all(o["inverse_function_type"] == "isigmoid" for o in opts) else BAR64_INORMAL
     for pb in sorted({B, 1}, reverse=True):
-        tally = Tally("%s pb %d" % (desc, pb))
+        tally = fdr.Tally("%s pb %d" % (desc, pb), TOTALS)
         x = rng.normal(size=(B, D)) * 2.0
         x[:min(4, B - 1)] *= 8.0                                   # a few rows far out in the tails (not the only row of B = 1)
         params = rng.normal(size=(pb, P)) * 0.8
@@ -259,7 +213,7 @@ def test_pdf_gradients_vs_finite_differences(cfg):
     named = {k: (p.grad.double().cpu().numpy() if p.grad is not None else np.zeros(tuple(p.shape))) for k, p in pdf.named_parameters()}
     gx = tx.grad.double().cpu().numpy()
     gc = None if tc is None else tc.grad.double().cpu().numpy()
-    tally = Tally("%s %s %s %s" % (pdf_defs, flow_defs, kw, str(dtype).split(".")[-1]))
+    tally = fdr.Tally("%s %s %s %s" % (pdf_defs, flow_defs, kw, str(dtype).split(".")[-1]), TOTALS)
 
     def bar_scale(got, fd):                                        # float64: of the FD's scale; float32: of the tensor's largest entry
         return (BAR64, fd) if dtype == torch.float64 else (BAR32, np.max(np.abs(got)))
