@@ -51,11 +51,20 @@ __device__ __forceinline__ void cond_mchain_body(const Args& a, const int block,
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, lq = lane >> 4;
     const int64_t last = a.B - 1;
+    // float32: W1 and b1 are staged times 2 log2(e), so the K1 -> 128 product (started from the bias) IS the v_exp_f32 argument of tanh (as cs_hidden)
+    constexpr bool F32 = std::is_same<T, float>::value;
+    constexpr T PRE = F32 ? T(2.8853900817779268) : T(1);
     for (int i = tid; i < CM_HMAX * k1p; i += NT) {
         const int r = i / k1p, c = i - r * k1p;
-        W1s[r * ldk + c] = (r < a.H && c < a.K1) ? a.W1[(int64_t)r * a.w1s + c] : T(0);
+        T w = (r < a.H && c < a.K1) ? a.W1[(int64_t)r * a.w1s + c] : T(0);
+        if constexpr (F32) w *= PRE;
+        W1s[r * ldk + c] = w;
     }
-    for (int i = tid; i < CM_HMAX; i += NT) b1s[i] = i < a.H ? a.b1[i] : T(0);
+    for (int i = tid; i < CM_HMAX; i += NT) {
+        T b = i < a.H ? a.b1[i] : T(0);
+        if constexpr (F32) b *= PRE;
+        b1s[i] = b;
+    }
     float w2_inv = 1.f;                                              // float32: 2^-(e + 14), undoes the scales of W2 and h
     if constexpr (std::is_same<T, float>::value) {
         // absmax of W2 -> the power of two that puts it into [2^14, 2^15) (f16 normal range for the low pieces as well: jf_cond_split.h)
@@ -102,50 +111,81 @@ __device__ __forceinline__ void cond_mchain_body(const Args& a, const int block,
     // not once per 256 rows (4096 workgroups each spent ~5 us on three dependent rounds of L2 loads before their first MFMA)
     for (int64_t row0 = (int64_t)block * NT; row0 < a.B; row0 += (int64_t)n_blocks * NT) {
     __syncthreads();                                               // the previous tile's readers of Xs / tiles are done
-    for (int i = tid; i < NT * k1p; i += NT) {
-        const int r = i / k1p, c = i - r * k1p;
-        const int64_t gr = row0 + r;
-        Xs[r * ldk + c] = c < a.K1 ? a.in[(gr <= last ? gr : last) * a.in_stride + c] : T(0);
+    if constexpr (F32) {
+        // thread t owns row t of the tile (NT rows, NT threads) and walks its K1 contiguous inputs, eight per turn: no index division; a turn's
+        // loads are issued before its first LDS write.  Rows past B replicate row B-1
+        constexpr int CG = 8;
+        const int64_t gr = row0 + tid;
+        const T* src = a.in + (gr <= last ? gr : last) * a.in_stride;
+        T* xr = Xs + tid * ldk;
+        for (int c0 = 0; c0 < k1p; c0 += CG) {
+            T v[CG];
+#pragma unroll
+            for (int u = 0; u < CG; ++u) v[u] = c0 + u < a.K1 ? src[c0 + u] : T(0);
+#pragma unroll
+            for (int u = 0; u < CG; ++u)
+                if (c0 + u < k1p) xr[c0 + u] = v[u];
+        }
+    } else {
+        // (float64 keeps the element-wise form: the kernel sits at the register ceiling, and the row walk's loads in flight spilt 20 bytes)
+        for (int i = tid; i < NT * k1p; i += NT) {
+            const int r = i / k1p, c = i - r * k1p;
+            const int64_t gr = row0 + r;
+            Xs[r * ldk + c] = c < a.K1 ? a.in[(gr <= last ? gr : last) * a.in_stride + c] : T(0);
+        }
     }
     __syncthreads();
 
     // ---- parameters of the wave's 64 rows -> its LDS tile, 16 rows at a time
     T* tile = tiles + wave * 64 * a.tile_stride;
+#pragma unroll 1                                                   // (the compiler unrolls the slim body four times: 6 registers, and nothing gained)
     for (int rt = 0; rt < 4; ++rt) {
         T hreg[JH][NREG];
+        f16x8 hH[CS_KSTEPS], hL[CS_KSTEPS];                            // float32: the activations as f16 pairs in the B-operand layout (as cs_hidden)
         {
             typename MF::Acc acc[JH];
 #pragma unroll
-            for (int j = 0; j < JH; ++j)
+            for (int j = 0; j < JH; ++j) {
+                // float32: the accumulators start from the bias (register r of tile j = hidden unit 16 j + 4 lq + r)
+                if constexpr (F32) acc[j] = *reinterpret_cast<const f32x4*>(b1s + j * MT + 4 * lq);
+                else {
 #pragma unroll
-                for (int r = 0; r < NREG; ++r) acc[j][r] = T(0);
+                    for (int r = 0; r < NREG; ++r) acc[j][r] = T(0);
+                }
+            }
             for (int s = 0; s < k1p / KS; ++s) {
                 const int kk = s * KS + lq;
                 const T xb = Xs[(wave * 64 + rt * MT + li) * ldk + kk];
 #pragma unroll
                 for (int j = 0; j < JH; ++j) acc[j] = MF::mma(W1s[(j * MT + li) * ldk + kk], xb, acc[j]);
             }
+            if constexpr (F32) {
+                // h 2^14 = 2^14 (1 - 2 / (e^{2a} + 1)) in one fma behind the reciprocal, the split's residual as v_fma_mix_f32 on the packed f16
+                // half (cs_split16_plain): 4 vector + 2 transcendental instructions per hidden value
 #pragma unroll
-            for (int j = 0; j < JH; ++j)
+                for (int s = 0; s < CS_KSTEPS; ++s) {
+                    using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
+                    u32x4 q0, q1;
 #pragma unroll
-                for (int r = 0; r < NREG; ++r) hreg[j][r] = M<T>::tanh_fast(acc[j][r] + b1s[j * MT + MF::row_of(r, lane)]);
-        }
-        if constexpr (std::is_same<T, float>::value) {
-            // activations -> f16 pairs in the B-operand layout (as cs_hidden), then three MFMA passes per (column tile, k-step): lo x hi, hi x lo, hi x hi
-            f16x8 hH[CS_KSTEPS], hL[CS_KSTEPS];
-#pragma unroll
-            for (int s = 0; s < CS_KSTEPS; ++s) {
-                using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-                u32x4 q0, q1;
-#pragma unroll
-                for (int i = 0; i < 8; i += 2) {
-                    const int j = 2 * s + (i >> 2), r = i & 3;
-                    unsigned ph, pl;
-                    cs_split16(hreg[j][r] * CS_H_SCALE, hreg[j][r + 1] * CS_H_SCALE, ph, pl);
-                    q0[i >> 1] = ph; q1[i >> 1] = pl;
+                    for (int i = 0; i < 8; i += 2) {
+                        const int j = 2 * s + (i >> 2), r = i & 3;
+                        const float t0 = fmaf(-2.0f * CS_H_SCALE, __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(acc[j][r]) + 1.0f), CS_H_SCALE);
+                        const float t1 = fmaf(-2.0f * CS_H_SCALE, __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(acc[j][r + 1]) + 1.0f), CS_H_SCALE);
+                        unsigned ph, pl;
+                        cs_split16_plain(t0, t1, ph, pl);
+                        q0[i >> 1] = ph; q1[i >> 1] = pl;
+                    }
+                    hH[s] = __builtin_bit_cast(f16x8, q0); hL[s] = __builtin_bit_cast(f16x8, q1);
                 }
-                hH[s] = __builtin_bit_cast(f16x8, q0); hL[s] = __builtin_bit_cast(f16x8, q1);
+            } else {
+#pragma unroll
+                for (int j = 0; j < JH; ++j)
+#pragma unroll
+                    for (int r = 0; r < NREG; ++r) hreg[j][r] = M<T>::tanh_fast(acc[j][r] + b1s[j * MT + MF::row_of(r, lane)]);
             }
+        }
+        if constexpr (F32) {
+            // three MFMA passes per (column tile, k-step): lo x hi, hi x lo, hi x hi
             const unsigned char* W2p = reinterpret_cast<const unsigned char*>(W2s);
             for (int ct = 0; ct < np / MT; ++ct) {
                 f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -185,7 +225,11 @@ __device__ __forceinline__ void cond_mchain_body(const Args& a, const int block,
     __syncthreads();
 
     // ---- the layers, lane-per-row (as mchain_kernel)
-    const int64_t row = row0 + tid;
+    // (the lane index behind an empty asm: what the layers derive from it -- row number, tile and table addresses -- is then formed here, not
+    //  hoisted out of the tile loop into registers that stay live across the hidden layer)
+    int lt = tid;
+    asm volatile("" : "+v"(lt));
+    const int64_t row = row0 + lt;
     const bool active = row <= last;
     const int64_t rrow = active ? row : last;
     T x[3] = {T(0), T(0), T(0)};
@@ -193,15 +237,15 @@ __device__ __forceinline__ void cond_mchain_body(const Args& a, const int block,
     for (int d = 0; d < Fam::DIM; ++d) if (d < a.dim) x[d] = a.x[rrow * a.xs + d];
     T ld = a.ld_in ? a.ld_in[rrow] : T(0);
     LaneCtx<T> ctx;
-    ctx.tab = tabs + tid * (a.tab + a.scratch);
+    ctx.tab = tabs + lt * (a.tab + a.scratch);
     ctx.corr = ctx.tab + a.tab;
     ctx.bins = nullptr; ctx.bin_i = 0;
     ctx.oob = ctx.nonconv = ctx.nonfinite = false;
     ctx.lane_valid = active;
-    const T* prow = tiles + tid * a.tile_stride;
+    const T* prow = tiles + lt * a.tile_stride;
     for (int i = 0; i < a.n_layers; ++i) {
         const int l = FWD ? i : a.n_layers - 1 - i;
-        Fam::template apply<T, FWD>(a.L[l], prow + a.col0[l], x, ld, ctx);
+        apply_hot<Fam, T, FWD>(a.L[l], prow + a.col0[l], x, ld, ctx);
     }
     bool bad = !M<T>::finite(ld);
 #pragma unroll

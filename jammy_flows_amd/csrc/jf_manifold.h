@@ -7,6 +7,7 @@
 // wrapped by the sphere_base rotation / chart steps (jammy_flows/layers/spheres/sphere_base.py:601-695).
 // Every family exposes  apply<FWD>(layer, row, x[3], log_det, ctx)  on INTRINSIC coordinates.
 #pragma once
+#include <type_traits>
 #include "jf_sphere.h"
 #include "jf_spline.h"
 
@@ -435,6 +436,51 @@ struct FFam {
         } else { x[0] = th; x[1] = angle; }
     }
 
+    // log-prob direction, middle: the nested spline flows on (cos theta, azimuth) between head and tail (fvm_2d.py:406-432)
+    template <typename T> static __device__ __forceinline__ void inv_nested(const CLayer& L, const T* __restrict__ vert, const T* __restrict__ circ, int nv,
+                                                                            T region, T& ret, T& angle, T& ld, LaneCtx<T>& c) {
+        const bool inside = (region == T(0)) || ((ret > T(-1) + region) && (ret < T(1) - region));
+        if (L.correlated) {                                                             // :406-409: nested i1+s1 passthrough pdf, inverse direction
+            if (inside) {
+                const T z_in = ret;                                                     // block 1 is conditioned on block 0's TARGET value
+                int off = nv;
+                for (int i = L.n_vertical - 1; i >= 0; --i) {
+                    off -= spline_row_len(L.vertical[i].sp);
+                    ret = r_core<T>(L.vertical[i], vert + off, ret, ld, c, true);
+                }
+                corr_mlp<T>(L, vert + nv, z_in, c.corr);
+                int coff = corr_out(L);
+                for (int i = L.n_circular - 1; i >= 0; --i) {
+                    coff -= rot_len(L.circular[i].hh_iter, 2) + spline_row_len(L.circular[i].sp);
+                    T xx[3] = {angle, T(0), T(0)};
+                    OFam::apply<T, false>(L.circular[i], c.corr + coff, xx, ld, c);
+                    angle = xx[0];
+                }
+            } else {
+                for (int i = 0; i < L.n_vertical + L.n_circular; ++i) c.put_bin(-2);
+            }
+        } else {
+        if (L.n_circular > 0) {                                                         // :416-427 (layers in reverse, tail-first)
+            const T sc = azimuthal_scaling<T>(ret);
+            int off = 0;
+            for (int i = 0; i < L.n_circular; ++i) off += spline_row_len(L.circular[i].sp);
+            for (int i = L.n_circular - 1; i >= 0; --i) {
+                off -= spline_row_len(L.circular[i].sp);
+                if (inside) angle = o_core<T>(L.circular[i], circ + off, angle, ld, c, false, sc);
+                else c.put_bin(-2);
+            }
+        }
+        if (L.n_vertical > 0) {                                                         // :430-432
+            int off = nv;
+            for (int i = L.n_vertical - 1; i >= 0; --i) {
+                off -= spline_row_len(L.vertical[i].sp);
+                if (inside) ret = r_core<T>(L.vertical[i], vert + off, ret, ld, c, true);
+                else c.put_bin(-2);
+            }
+        }
+        }
+    }
+
     template <typename T, bool FWD> static __device__ __forceinline__ void apply(const CLayer& L, const T* __restrict__ p, T (&x)[3], T& ld, LaneCtx<T>& c) {
         const T* fp = p + rot_len(L.hh_iter, 3);
         const T zs = (T)L.z_sign, region = (T)L.identity_region;
@@ -446,46 +492,7 @@ struct FFam {
         if constexpr (!FWD) {
             T ret, angle;
             inv_head<T>(L, p, x, ld, ret, angle);
-            const bool inside = (region == T(0)) || ((ret > T(-1) + region) && (ret < T(1) - region));
-            if (L.correlated) {                                                             // :406-409: nested i1+s1 passthrough pdf, inverse direction
-                if (inside) {
-                    const T z_in = ret;                                                     // block 1 is conditioned on block 0's TARGET value
-                    int off = nv;
-                    for (int i = L.n_vertical - 1; i >= 0; --i) {
-                        off -= spline_row_len(L.vertical[i].sp);
-                        ret = r_core<T>(L.vertical[i], vert + off, ret, ld, c, true);
-                    }
-                    corr_mlp<T>(L, vert + nv, z_in, c.corr);
-                    int coff = corr_out(L);
-                    for (int i = L.n_circular - 1; i >= 0; --i) {
-                        coff -= rot_len(L.circular[i].hh_iter, 2) + spline_row_len(L.circular[i].sp);
-                        T xx[3] = {angle, T(0), T(0)};
-                        OFam::apply<T, false>(L.circular[i], c.corr + coff, xx, ld, c);
-                        angle = xx[0];
-                    }
-                } else {
-                    for (int i = 0; i < L.n_vertical + L.n_circular; ++i) c.put_bin(-2);
-                }
-            } else {
-            if (L.n_circular > 0) {                                                         // :416-427 (layers in reverse, tail-first)
-                const T sc = azimuthal_scaling<T>(ret);
-                int off = 0;
-                for (int i = 0; i < L.n_circular; ++i) off += spline_row_len(L.circular[i].sp);
-                for (int i = L.n_circular - 1; i >= 0; --i) {
-                    off -= spline_row_len(L.circular[i].sp);
-                    if (inside) angle = o_core<T>(L.circular[i], circ + off, angle, ld, c, false, sc);
-                    else c.put_bin(-2);
-                }
-            }
-            if (L.n_vertical > 0) {                                                         // :430-432
-                int off = nv;
-                for (int i = L.n_vertical - 1; i >= 0; --i) {
-                    off -= spline_row_len(L.vertical[i].sp);
-                    if (inside) ret = r_core<T>(L.vertical[i], vert + off, ret, ld, c, true);
-                    else c.put_bin(-2);
-                }
-            }
-            }
+            inv_nested<T>(L, vert, circ, nv, region, ret, angle, ld, c);
             inv_tail<T>(L, ret, angle, x, ld);
         } else {
             if (L.first) {
@@ -544,6 +551,87 @@ struct FFam {
             if (L.hh_iter != 0) s2_rotate<T>(p, L.hh_iter, x, ld, false);
         }
     }
+
+    // The float32 log-prob direction of the forward kernels (apply_hot below; the float64 path, the sampling direction and the adjoints run
+    // apply / inv_head / inv_tail above).  The same map as apply<float, false>, with the angle <-> embedding round trips it does not need
+    // taken out and hardware forms where the argument is bounded by construction:
+    //  * between the rotation and the plane chart the point is carried as (cos theta, cos phi, sin phi) read off the rotated embedding
+    //    vector; apply goes acos -> cos for theta and acos -> cos / sin for phi.  The azimuth itself is formed (azimuth(), as before) only where
+    //    something reads it: nested circular flows, the correlated variant, the quarter turn, a layer that is not the first of its block
+    //  * apply adds log sin theta' after the rotation and takes it off again one line later, and likewise around the plane chart (acos(ret) lies
+    //    in [4.9e-4, pi - 4.9e-4] after safe_cos, inside safe_angle_pi's window: both terms are the same number).  Neither pair is evaluated
+    //  * the one log sin theta that stays is that of the INPUT angle.  Near a pole it dominates the result, so sine and cosine of theta come
+    //    from sincos_polar (relative accuracy at both poles), not from v_sin_f32; its logarithm is v_log_f32: sin theta in [1e-7, 1] is normal
+    //  * phi in [0, 2 pi] enters only through the direction (cos phi, sin phi): v_cos_f32 / v_sin_f32
+    //  * divisions whose quotient is used as it is (reflections, normalisation, the vMF quotient) are v_rcp_f32 / v_rsq_f32 of normal numbers
+    // Kept precise: kappa and every exponential / logarithm of it (expm1 at small kappa; the two exponentials of the vMF quotient, whose
+    // difference is divided by 1 - e^{-2 kappa}), the logarithm under the chart's square root (relative accuracy near 1), every nested flow.
+    static __device__ __forceinline__ void apply_inv_f32(const CLayer& L, const float* __restrict__ p, float (&x)[3], float& ld, LaneCtx<float>& c) {
+        using T = float;
+        const T* fp = p + rot_len(L.hh_iter, 3);
+        const T zs = (T)L.z_sign, region = (T)L.identity_region;
+        const T kappa = kappa_of<T>(L, p, fp);
+        int nv = 0;
+        for (int i = 0; i < L.n_vertical; ++i) nv += spline_row_len(L.vertical[i].sp);
+        const T* vert = fp + n_kappa(L);
+        const T* circ = vert + nv;
+        const bool need_angle = L.extra_rotation || L.correlated || L.n_circular > 0 || !L.first;
+        T st, prev;
+        M<T>::sincos_polar(safe_angle_pi<T>(x[0]), st, prev);
+        ld += M<T>::log_fast(st);
+        T angle = x[1], cphi = T(1), sphi = T(0);
+        bool have_cs = false;
+        if (L.hh_iter != 0) {
+            T sp, cp;
+            M<T>::sincos_turn(x[1], sp, cp);
+            T e[3] = {st * cp, st * sp, prev};
+            if (L.hh_iter > 0) {
+                for (int i = 0; i < L.hh_iter; ++i) {                                    // Q^T e: H_0 first (reflect_raw with v_rcp_f32)
+                    const T* v = p + 3 * i;
+                    const T f = T(2) * (v[0] * e[0] + v[1] * e[1] + v[2] * e[2]) * M<T>::rcp(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+                    e[0] -= f * v[0]; e[1] -= f * v[1]; e[2] -= f * v[2];
+                }
+            } else rotate_embed<T, 3>(p, L.hh_iter, e, true);
+            const T rho2 = e[0] * e[0] + e[1] * e[1];                                    // |e| = 1 up to rounding: rho2 + e2^2 is normal
+            const T q = e[2] * M<T>::rsq(rho2 + e[2] * e[2]);
+            prev = q > T(1) ? T(1) : (q < T(-1) ? T(-1) : q);                            // (a NaN stays a NaN)
+            if (need_angle) angle = azimuth<T>(e[0], e[1]);
+            else {
+                const bool pole = !(rho2 > T(1e-30));                                    // azimuth() gives phi = 0 at rho = 0
+                const T ir = M<T>::rsq(pole ? T(1) : rho2);
+                cphi = pole ? T(1) : e[0] * ir; sphi = pole ? T(0) : e[1] * ir;
+                have_cs = true;
+            }
+        }
+        const T e2k = M<T>::exp(T(-2) * kappa);
+        const T safe = kappa < T(100) ? M<T>::log(M<T>::expm1(T(2) * kappa)) : T(2) * kappa;
+        ld += M<T>::log(T(2) * kappa) + kappa * (zs * prev + T(1)) - safe;
+        T ret = zs * ((T(1) + e2k - T(2) * M<T>::exp(kappa * (zs * prev - T(1)))) * M<T>::rcp(T(-1) + e2k));
+        if (kappa < M<T>::KAPPA_ID) ret = prev;
+        ret = safe_cos<T>(ret, M<T>::EPS_COS);
+        if (L.extra_rotation) inbetween<T>(ret, angle, ld, true);
+        inv_nested<T>(L, vert, circ, nv, region, ret, angle, ld, c);
+        ret = safe_cos<T>(ret, M<T>::EPS_COS);
+        if (L.first) {
+            const T om = T(1) - safe_cos<T>(ret, T(1e-6));                               // in [1e-6, 2)
+            const T lh = M<T>::log(om * T(0.5));
+            ld -= lh + T(0.69314718055994531);
+            const T r = M<T>::sqrt_fast(T(-2) * lh);
+            if (!have_cs) M<T>::sincos_turn(angle, sphi, cphi);                          // an azimuth: [0, 2 pi]
+            x[0] = r * cphi; x[1] = r * sphi;
+        } else {
+            x[0] = M<T>::acos(ret);
+            ld -= T(0.5) * M<T>::log_fast((T(1) - ret) * (T(1) + ret));                  // sin(acos(ret))^2 >= 2.3e-7: normal
+            x[1] = angle;
+        }
+    }
 };
+
+// one layer of a forward kernel: the family's apply, except for the float32 log-prob direction of 'f'
+template <class Fam, typename T, bool FWD>
+__device__ __forceinline__ void apply_hot(const typename Fam::CLayer& L, const T* __restrict__ p, T (&x)[3], T& ld, LaneCtx<T>& c) {
+    if constexpr (std::is_same<Fam, FFam>::value && std::is_same<T, float>::value && !FWD) FFam::apply_inv_f32(L, p, x, ld, c);
+    else Fam::template apply<T, FWD>(L, p, x, ld, c);
+}
 
 }  // namespace jf

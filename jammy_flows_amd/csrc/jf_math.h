@@ -50,6 +50,34 @@ template <> struct M<float> {
     static __device__ __forceinline__ float sqrt_fast(float x) { return __builtin_amdgcn_sqrtf(x); }
     static __device__ __forceinline__ float rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 #endif
+    static __device__ __forceinline__ float rsq(float x) { return __builtin_amdgcn_rsqf(x); }                       // v_rsq_f32 (normal-range inputs only)
+    // sine and cosine of an azimuth on v_sin_f32 / v_cos_f32 (argument in turns, valid to +-256 turns; ~1e-6 ABSOLUTE): for angles that are
+    // bounded by construction (phi in [0, 2 pi]) and whose sine / cosine enter as a direction, never through a logarithm
+    static __device__ __forceinline__ void sincos_turn(float x, float& s, float& c) {
+        const float t = x * 0.15915494309189535f;
+        s = __builtin_amdgcn_sinf(t); c = __builtin_amdgcn_cosf(t);
+    }
+    // sine and cosine of a polar angle in [0, pi]; the sine to a RELATIVE 1.6e-7 also at the poles (log sin theta is a term of the log-density),
+    // the cosine to an absolute 1.3e-7 (numpy emulation over 2.2e6 angles, dense at both poles): u = distance to the nearer pole (pi in two
+    // pieces, the subtraction is exact), Taylor polynomials of sin u / u and cos u on [0, pi/2] (first dropped terms u^12 / 13! <= 5.7e-8 and
+    // u^14 / 14! <= 6.4e-9).  No argument reduction: OCML's sinf / cosf carry the full-range one
+    static __device__ __forceinline__ void sincos_polar(float th, float& s, float& c) {
+        const bool up = th > 1.57079632679489662f;
+        const float u = up ? (3.14159274101257324f - th) + -8.74227765734758577e-8f : th;
+        const float z = u * u;
+        float ps = fmaf(z, -2.50521083854417188e-8f, 2.75573192239858907e-6f);
+        ps = fmaf(z, ps, -1.98412698412698413e-4f);
+        ps = fmaf(z, ps, 8.33333333333333333e-3f);
+        ps = fmaf(z, ps, -1.66666666666666667e-1f);
+        s = fmaf(u * z, ps, u);
+        float pc = fmaf(z, 2.08767569878680990e-9f, -2.75573192239858907e-7f);
+        pc = fmaf(z, pc, 2.48015873015873016e-5f);
+        pc = fmaf(z, pc, -1.38888888888888889e-3f);
+        pc = fmaf(z, pc, 4.16666666666666667e-2f);
+        pc = fmaf(z, pc, -0.5f);
+        pc = fmaf(z, pc, 1.0f);
+        c = up ? -pc : pc;
+    }
     static __device__ __forceinline__ float exp(float x) { return expf(x); }
     static __device__ __forceinline__ float log(float x) { return logf(x); }
     static __device__ __forceinline__ float log1p(float x) { return log1pf(x); }

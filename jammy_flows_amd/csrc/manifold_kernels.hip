@@ -93,7 +93,7 @@ __global__ void __launch_bounds__(64) mchain_kernel(const MChainArgs<T, typename
                 ctx.tab_built = true;
             }
         }
-        if (lane_in) Fam::template apply<T, FWD>(a.L[l], prow, x, ld, ctx);
+        if (lane_in) apply_hot<Fam, T, FWD>(a.L[l], prow, x, ld, ctx);
     }
     bool bad = !M<T>::finite(ld);
 #pragma unroll
