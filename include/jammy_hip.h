@@ -812,6 +812,33 @@ int jf_pair_mchain_f32(int32_t fam, const float* x, int64_t xs, const float* par
 int jf_pair_mchain_f64(int32_t fam, const double* x, int64_t xs, const double* params, int64_t ps, int64_t n_groups, int32_t S, int32_t i0, int32_t i1,
                        int32_t n_layers, const void* layers, const double* add, double* tile, double* out, int32_t* status, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Rectangular pair evaluation (pdf.log_prob_on_grid / pdf.marginal_log_prob): the tile of the pairwise entry points above for J parameter
+ * rows against N targets per group, returned instead of reduced.  Targets x (default coordinates of ONE block, row stride xs), the target set
+ * of group g starting at row g * xgs: xgs = N (or more) = per-group targets, xgs = 0 = one target set shared by all groups; parameter rows
+ * params (n_groups * J, P; row stride ps, or ps = 0: one permanent row for all).  For the targets i in [i0, i1) of every group
+ *
+ *     tile[(g * J + j) * (i1 - i0) + (i - i0)] = logN(f^-1(x[g,i]; params[g,j])) + log_det(x[g,i]; params[g,j])
+ *
+ * One workgroup stages and derives ONE parameter row (g, j) and walks the targets against it, as for the pairwise entry points -- which are
+ * the case J = N = S, xgs = S of the same kernels; a tile value depends on nothing but its own target and parameter row.  The limits are
+ * those of jf_pair_gf / jf_pair_mchain ('v': float64 only; n_groups * J <= 2^31 - 1), otherwise JF_ERR_UNSUPPORTED.  JF_ERR_BADARG: null
+ * x / params / tile, J < 1, i0 < 0, i1 < i0, i1 > N, xgs neither 0 nor >= i1.  Solver status through `status` (nullable).
+ * jf_grid_reduce: out[g * ni + i] = add[g * ni + i] + log( sum_j exp( tile[g, j, i] + logw[g * J + j] ) ), j in the fixed order 0 .. J-1, no
+ *   atomics; add is nullable (= 0); logw = NULL: uniform weights 1 / J, computed as m + log(s) - log(J) (the bits of the pairwise reduction).
+ *   JF_ERR_BADARG: null tile / out, J < 1, negative n_groups / ni; JF_ERR_UNSUPPORTED: n_groups * J > 2^31 - 1 (no jf_grid_* tile is larger).
+ * ------------------------------------------------------------------------------------------------------------ */
+int jf_grid_gf_f32(const float* x, int64_t xs, int64_t xgs, const float* params, int64_t ps, int64_t n_groups, int32_t J, int32_t N, int32_t i0,
+                   int32_t i1, int32_t D, int32_t n_layers, const jf_gf_layer* layers, float* tile, int32_t* status, void* stream);
+int jf_grid_gf_f64(const double* x, int64_t xs, int64_t xgs, const double* params, int64_t ps, int64_t n_groups, int32_t J, int32_t N, int32_t i0,
+                   int32_t i1, int32_t D, int32_t n_layers, const jf_gf_layer* layers, double* tile, int32_t* status, void* stream);
+int jf_grid_mchain_f32(int32_t fam, const float* x, int64_t xs, int64_t xgs, const float* params, int64_t ps, int64_t n_groups, int32_t J, int32_t N,
+                       int32_t i0, int32_t i1, int32_t n_layers, const void* layers, float* tile, int32_t* status, void* stream);
+int jf_grid_mchain_f64(int32_t fam, const double* x, int64_t xs, int64_t xgs, const double* params, int64_t ps, int64_t n_groups, int32_t J, int32_t N,
+                       int32_t i0, int32_t i1, int32_t n_layers, const void* layers, double* tile, int32_t* status, void* stream);
+int jf_grid_reduce_f32(const float* tile, const float* logw, const float* add, int64_t n_groups, int32_t J, int32_t ni, float* out, void* stream);
+int jf_grid_reduce_f64(const double* tile, const double* logw, const double* add, int64_t n_groups, int32_t J, int32_t ni, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -162,6 +162,9 @@ _SIGNATURES = {
     "jf_segment_moments": [_P, _I64, _P, _I64, _I64, _I32, _P, _P, _P, _P],
     "jf_pair_gf": [_P, _I64, _P, _I64, _I64, _I32, _I32, _I32, _I32, _I32, ctypes.POINTER(jf_gf_layer), _P, _P, _P, _P, _P],
     "jf_pair_mchain": [_I32, _P, _I64, _P, _I64, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P],
+    "jf_grid_gf": [_P, _I64, _I64, _P, _I64, _I64, _I32, _I32, _I32, _I32, _I32, _I32, ctypes.POINTER(jf_gf_layer), _P, _P, _P],
+    "jf_grid_mchain": [_I32, _P, _I64, _I64, _P, _I64, _I64, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P],
+    "jf_grid_reduce": [_P, _P, _P, _I64, _I32, _I32, _P, _P],
     "jf_amlp_stage": [_P, _I64, _P, _I64, _I64, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P, _I64, _P],
     "jf_amlp_stage_bwd": [_P, _I64, _P, _I64, _I64, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P],
     "jf_t_layer_inv": [_P, _I64, _P, _P, _I64, _I32, _I64, _I32, ctypes.POINTER(jf_t_layer), _P, _I64, _P, _P, _P, _P, _P],
@@ -1619,6 +1622,71 @@ def pair_logmeanexp(kind, x, params, n_params, n_groups, S, i0, i1, layers, dim,
                                                       ctypes.cast(arr, ctypes.c_void_p), _ptr(add), _ptr(tile), _ptr(out), _ptr(status)), dev,
                      unsupported_ok=True)
     return out if ok else None
+
+
+def grid_logp(kind, x, params, n_params, n_groups, J, N, layers, dim, i0=0, i1=None, shared_targets=False, tile=None, status=None):
+    """rectangular pair evaluation (jf_grid_gf / jf_grid_mchain): J parameter rows against N targets per group,
+
+        tile[g, j, i - i0] = log N(f^-1(x[g,i]; params[g,j])) + log_det(x[g,i]; params[g,j])        for the targets i in [i0, i1)
+
+    kind, layers, n_params, dim: as pair_logmeanexp.  x: the block's targets in default coordinates, (n_groups * N, dim), or with
+    shared_targets (N, dim): one target set for all groups.  params (n_groups * J, P) or (1, P) (one permanent row) or None (a chain without
+    parameters).  `tile` (n_groups, J, i1 - i0) is created when absent.  Returns tile, or None when the library declines the chain
+    (JF_ERR_UNSUPPORTED): the caller then takes its generic path."""
+    dev = require_device(x, params, tile, status)
+    x = _rowmajor(x)
+    i1 = N if i1 is None else i1
+    x_rows = N if shared_targets else n_groups * N
+    if x.shape != (x_rows, dim):
+        raise ValueError("grid_logp: expected targets of shape (%d, %d), got %s" % (x_rows, dim, tuple(x.shape)))
+    if J < 1 or not (0 <= i0 <= i1 <= N):
+        raise ValueError("grid_logp: bad sizes J = %d, target range [%d, %d) of N = %d" % (J, i0, i1, N))
+    rows = n_groups * J
+    n_layers = len(layers)
+    params, pptr, pstride, pb = _param_rows(params, rows, x.dtype, "grid_logp")
+    if (0 if params is None else params.shape[1]) != int(n_params):
+        raise ValueError("grid_logp: the chain takes %d parameters per row, got %s" % (n_params, "none" if params is None else params.shape[1]))
+    if pb == 1 and rows != 1:
+        pstride = 0          # these entry points take no param_batch: one permanent row is a row stride of 0
+    shape = (n_groups, J, i1 - i0)
+    if tile is None:
+        tile = torch.empty(shape, dtype=x.dtype, device=x.device)
+    elif tile.dtype != x.dtype or tuple(tile.shape) != shape or not tile.is_contiguous():
+        raise ValueError("grid_logp: tile must be a contiguous %s tensor of the input dtype" % (shape,))
+    xgs = 0 if shared_targets else N
+    suf = _suffix(x)
+    if kind == "g":
+        ok = _launch("jf_grid_gf" + suf, "grid", (_ptr(x), x.stride(0), xgs, pptr, pstride, n_groups, J, N, i0, i1, dim, n_layers, layers, _ptr(tile),
+                                                  _ptr(status)), dev, unsupported_ok=True)
+    else:
+        arr = mchain_layer_array(kind, layers)
+        ok = _launch("jf_grid_mchain" + suf, "grid", (ord(kind), _ptr(x), x.stride(0), xgs, pptr, pstride, n_groups, J, N, i0, i1, n_layers,
+                                                      ctypes.cast(arr, ctypes.c_void_p), _ptr(tile), _ptr(status)), dev, unsupported_ok=True)
+    return tile if ok else None
+
+
+def grid_reduce(tile, logw=None, add=None):
+    """tile (n_groups, J, ni) -> out (n_groups, ni): out[g, i] = add[g, i] + log sum_j exp(tile[g, j, i] + logw[g, j]) (jf_grid_reduce), j in
+    the fixed order 0 .. J-1.  logw (n_groups, J) or None: uniform weights 1 / J (the log-mean-exp of pair_logmeanexp, bit for bit); add
+    (n_groups, ni) or None."""
+    dev = require_device(tile, logw, add)
+    if tile.dim() != 3:
+        raise ValueError("grid_reduce: expected a (n_groups, J, ni) tile, got shape %s" % (tuple(tile.shape),))
+    tile = tile.contiguous()
+    G, J, ni = tile.shape
+    if J < 1:
+        raise ValueError("grid_reduce: J must be at least 1")
+    if logw is not None:
+        logw = logw.contiguous().reshape(-1)
+        if logw.dtype != tile.dtype or logw.shape[0] != G * J:
+            raise ValueError("grid_reduce: logw must be a (n_groups, J) tensor of the tile's dtype")
+    if add is not None:
+        add = add.contiguous().reshape(-1)
+        if add.dtype != tile.dtype or add.shape[0] != G * ni:
+            raise ValueError("grid_reduce: add must be a (n_groups, ni) tensor of the tile's dtype")
+    out = torch.empty((G, ni), dtype=tile.dtype, device=tile.device)
+    _launch("jf_grid_reduce" + _suffix(tile), "", (_ptr(tile), _ptr(logw), _ptr(add), G, J, ni, _ptr(out)), dev)
+    return out
 
 
 def amlp_stage(x, seg, n_in, n_out, rank, has_bias, act, residual=None):

@@ -13,6 +13,10 @@
 // (g, j), the S x S values never exist wider than one scalar per pair, and a pair's value depends on nothing but its own target and parameter
 // row.  The reduction walks j = 0 .. S-1 sequentially for each (g, i): its order is fixed, so out[g, i] carries the same bits for every
 // i-range, every number of groups in the launch and every grid (the project's row-independence rule).  No floating-point atomics.
+//
+// The same kernels evaluate RECTANGULAR tiles (jf_grid_gf / jf_grid_mchain / jf_grid_reduce, behind pdf.log_prob_on_grid and
+// pdf.marginal_log_prob): J parameter rows against N targets per group, the targets per group or shared by all groups, the tile returned
+// instead of reduced (PairDims below).  The pairwise entry points are the case J = N = S.
 #include <type_traits>
 
 #include "jf_gfb.h"
@@ -26,8 +30,12 @@ int gf_pair_fill_f64(GfChainArgs<double>& a, const double* p, int32_t D, int32_t
 static int gf_pair_fill(GfChainArgs<float>& a, const float* p, int32_t D, int32_t n, const jf_gf_layer* L, size_t& lds) { return gf_pair_fill_f32(a, p, D, n, L, lds); }
 static int gf_pair_fill(GfChainArgs<double>& a, const double* p, int32_t D, int32_t n, const jf_gf_layer* L, size_t& lds) { return gf_pair_fill_f64(a, p, D, n, L, lds); }
 
+// J parameter rows against N targets per group.  The pairwise entry points are the square case J = N = S with per-group targets (xgs = S);
+// the grid entry points take any J and N and, with xgs = 0, one target set shared by all groups.
 struct PairDims {
-    int S;                   // samples per group = parameter rows per group
+    int J;                   // parameter rows per group
+    int N;                   // targets per group
+    int64_t xgs;             // rows between the target sets of consecutive groups (N: per-group targets, 0: one set shared by all groups)
     int i0, ni;              // targets i0 .. i0 + ni of every group
 };
 
@@ -53,10 +61,10 @@ __global__ void __launch_bounds__(256, sizeof(T) == 8 ? 2 : 4) pair_gf_kernel(co
     const bool live = g < D, leader = g == 0;
     const int d = live ? g : D - 1;
     T* spl_tab = lds + a.tab_offset;
-    const int64_t gj = blockIdx.x;                        // = group * S + j
+    const int64_t gj = blockIdx.x;                        // = group * J + j
     derive_broadcast_from<T>(lds, a, a.params + gj * a.ps);
-    const int64_t grp = gj / pd.S;
-    const T* xg = a.x + (grp * pd.S + pd.i0) * a.xs;
+    const int64_t grp = gj / pd.J;
+    const T* xg = a.x + (grp * pd.xgs + pd.i0) * a.xs;
     T* out = tile_out + gj * pd.ni;
     const int n_layers = __builtin_amdgcn_readfirstlane(a.n_layers);
 
@@ -134,8 +142,8 @@ __global__ void __launch_bounds__(256) pair_gfb_kernel(const GfChainArgs<T> a, c
         }
     }
     __syncthreads();
-    const int64_t grp = gj / pd.S;
-    const T* xg = a.x + (grp * pd.S + pd.i0) * a.xs;
+    const int64_t grp = gj / pd.J;
+    const T* xg = a.x + (grp * pd.xgs + pd.i0) * a.xs;
     T* out = tile_out + gj * pd.ni;
     int n_bad = 0;
     const int step = (int)gridDim.y * 256;
@@ -208,41 +216,48 @@ template <typename T, int D> static int launch_pair_gfb(const GfChainArgs<T>& a,
 }
 
 // ---------------------------------------------------------------------------------------------------------- reduction over j
-template <typename T>
-__global__ void __launch_bounds__(256) pair_reduce_kernel(const T* __restrict__ tile, const T* __restrict__ add, int64_t n_groups, PairDims pd,
-                                                          T* __restrict__ out) {
+// out[g * ostride + o0 + i] = add[same] + log sum_j exp(tile[g, j, i] + logw[g * J + j]); WEIGHTED = false: uniform weights 1 / J, computed as
+// m + log(s) - log(J).  j runs 0 .. J-1 in this order for every (g, i).
+template <typename T, bool WEIGHTED>
+__global__ void __launch_bounds__(256) pair_reduce_kernel(const T* __restrict__ tile, const T* __restrict__ logw, const T* __restrict__ add,
+                                                          int64_t n_groups, int J, int ni, int64_t ostride, int o0, T* __restrict__ out) {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= n_groups * pd.ni) return;
-    const int64_t grp = t / pd.ni;
-    const int il = (int)(t - grp * pd.ni);
-    const T* p = tile + grp * pd.S * pd.ni + il;          // element j at p[j * ni]: consecutive lanes read consecutive words
+    if (t >= n_groups * ni) return;
+    const int64_t grp = t / ni;
+    const int il = (int)(t - grp * ni);
+    const T* p = tile + grp * J * ni + il;                // element j at p[j * ni]: consecutive lanes read consecutive words
+    const T* w = WEIGHTED ? logw + grp * J : nullptr;
     T m = -INFINITY;
-    for (int j = 0; j < pd.S; ++j) m = M<T>::max(m, p[(int64_t)j * pd.ni]);
+    for (int j = 0; j < J; ++j) m = M<T>::max(m, WEIGHTED ? p[(int64_t)j * ni] + w[j] : p[(int64_t)j * ni]);
     T s = T(0);
-    for (int j = 0; j < pd.S; ++j) s += M<T>::exp(p[(int64_t)j * pd.ni] - m);
-    const int64_t o = grp * pd.S + pd.i0 + il;
-    const T v = m + M<T>::log(s) - M<T>::log(T(pd.S));
+    for (int j = 0; j < J; ++j) s += M<T>::exp((WEIGHTED ? p[(int64_t)j * ni] + w[j] : p[(int64_t)j * ni]) - m);
+    const int64_t o = grp * ostride + o0 + il;
+    const T v = WEIGHTED ? m + M<T>::log(s) : m + M<T>::log(s) - M<T>::log(T(J));
     out[o] = add ? add[o] + v : v;
 }
-template <typename T> static int pair_reduce(const T* tile, const T* add, int64_t n_groups, const PairDims& pd, T* out, hipStream_t st) {
-    const int64_t n = n_groups * pd.ni;
-    jf::launch(pair_reduce_kernel<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, tile, add, n_groups, pd, out);
+template <typename T>
+static int pair_reduce(const T* tile, const T* logw, const T* add, int64_t n_groups, int J, int ni, int64_t ostride, int o0, T* out, hipStream_t st) {
+    const int64_t n = n_groups * ni;
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (logw) jf::launch(pair_reduce_kernel<T, true>, grid, dim3(256), 0, st, tile, logw, add, n_groups, J, ni, ostride, o0, out);
+    else jf::launch(pair_reduce_kernel<T, false>, grid, dim3(256), 0, st, tile, logw, add, n_groups, J, ni, ostride, o0, out);
     return check_launch();
 }
 
-static int pair_dims(int64_t n_groups, int32_t S, int32_t i0, int32_t i1, PairDims& pd) {
-    if (n_groups < 0 || S < 1 || i0 < 0 || i1 < i0 || i1 > S) return JF_ERR_BADARG;
-    if (n_groups * (int64_t)S > (int64_t)0x7fffffff) return JF_ERR_UNSUPPORTED;             // (one workgroup per parameter row: grid.x)
-    pd.S = S; pd.i0 = i0; pd.ni = i1 - i0;
+static int pair_dims(int64_t n_groups, int32_t J, int32_t N, int64_t xgs, int32_t i0, int32_t i1, PairDims& pd) {
+    if (n_groups < 0 || J < 1 || i0 < 0 || i1 < i0 || i1 > N || !(xgs == 0 || xgs >= i1)) return JF_ERR_BADARG;
+    if (n_groups > (int64_t)0x7fffffff || n_groups * (int64_t)J > (int64_t)0x7fffffff) return JF_ERR_UNSUPPORTED;   // (one workgroup per parameter row: grid.x)
+    pd.J = J; pd.N = N; pd.xgs = xgs; pd.i0 = i0; pd.ni = i1 - i0;
     return JF_OK;
 }
 
+// the tile alone: tile[(g * J + j) * ni + (i - i0)] for the targets [i0, i1) of every group
 template <typename T>
-static int pair_gf(const T* x, int64_t xs, const T* params, int64_t ps, int64_t n_groups, int32_t S, int32_t i0, int32_t i1, int32_t D, int32_t n_layers,
-                   const jf_gf_layer* layers, const T* add, T* tile, T* out, int32_t* status, void* stream) {
-    if (!x || !params || !tile || !out || xs < D || ps < 0) return JF_ERR_BADARG;
+static int grid_gf(const T* x, int64_t xs, int64_t xgs, const T* params, int64_t ps, int64_t n_groups, int32_t J, int32_t N, int32_t i0, int32_t i1,
+                   int32_t D, int32_t n_layers, const jf_gf_layer* layers, T* tile, int32_t* status, void* stream) {
+    if (!x || !params || !tile || xs < D || ps < 0) return JF_ERR_BADARG;
     PairDims pd{};
-    int rc = pair_dims(n_groups, S, i0, i1, pd);
+    int rc = pair_dims(n_groups, J, N, xgs, i0, i1, pd);
     if (rc != JF_OK) return rc;
     GfChainArgs<T> a{};
     size_t lds = 0;
@@ -250,7 +265,7 @@ static int pair_gf(const T* x, int64_t xs, const T* params, int64_t ps, int64_t 
     if (rc != JF_OK) return rc;
     if (n_groups == 0 || pd.ni == 0) return JF_OK;
     a.x = x; a.xs = xs; a.ps = ps; a.B = pd.ni; a.status = status;
-    const int64_t n_rows = n_groups * S;
+    const int64_t n_rows = n_groups * J;
     hipStream_t st = (hipStream_t)stream;
     // classic stretch, D <= 8, the component records fit: the lane = target walk (as gf_kernels.hip picks its lane = row broadcast kernel)
     bool classic = true;
@@ -271,8 +286,7 @@ static int pair_gf(const T* x, int64_t xs, const T* params, int64_t ps, int64_t 
             case 7: rc = launch_pair_gfb<T, 7>(a, pd, n_rows, lds_rows, tile, st); break;
             default: rc = launch_pair_gfb<T, 8>(a, pd, n_rows, lds_rows, tile, st); break;
         }
-        if (rc != JF_OK) return rc;
-        return pair_reduce<T>(tile, add, n_groups, pd, out, st);
+        return rc;
     }
     const int G = D <= 1 ? 1 : D <= 2 ? 2 : D <= 4 ? 4 : D <= 8 ? 8 : D <= 16 ? 16 : D <= 32 ? 32 : 64;
     switch (G) {
@@ -284,8 +298,17 @@ static int pair_gf(const T* x, int64_t xs, const T* params, int64_t ps, int64_t 
         case 32: rc = launch_pair_gf<T, 32>(a, pd, n_rows, lds, tile, st); break;
         default: rc = launch_pair_gf<T, 64>(a, pd, n_rows, lds, tile, st); break;
     }
-    if (rc != JF_OK) return rc;
-    return pair_reduce<T>(tile, add, n_groups, pd, out, st);
+    return rc;
+}
+
+// the pairwise entry point: the square case J = N = S of grid_gf with per-group targets, reduced over j with uniform weights
+template <typename T>
+static int pair_gf(const T* x, int64_t xs, const T* params, int64_t ps, int64_t n_groups, int32_t S, int32_t i0, int32_t i1, int32_t D, int32_t n_layers,
+                   const jf_gf_layer* layers, const T* add, T* tile, T* out, int32_t* status, void* stream) {
+    if (!x || !params || !tile || !out || xs < D || ps < 0) return JF_ERR_BADARG;
+    const int rc = grid_gf<T>(x, xs, S, params, ps, n_groups, S, S, i0, i1, D, n_layers, layers, tile, status, stream);
+    if (rc != JF_OK || n_groups == 0 || i1 == i0) return rc;
+    return pair_reduce<T>(tile, nullptr, add, n_groups, S, i1 - i0, S, i0, out, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------- manifold chains
@@ -331,8 +354,8 @@ __global__ void __launch_bounds__(64) pair_mchain_kernel(const MPairArgs<T, type
             __syncthreads();
         }
     }
-    const int64_t grp = gj / pd.S;
-    const T* xg = a.x + (grp * pd.S + pd.i0) * a.xs;
+    const int64_t grp = gj / pd.J;
+    const T* xg = a.x + (grp * pd.xgs + pd.i0) * a.xs;
     T* out = tile_out + gj * pd.ni;
 
     int n_bad = 0, n_oob = 0, n_nonconv = 0;
@@ -397,11 +420,11 @@ static bool pair_layer_ok(const jf_f_layer& L) {
 static bool pair_layer_ok(const jf_v_layer& L) { return L.exp_map_type >= 0 && L.exp_map_type <= JF_V_SPLINES; }
 
 template <typename T, class Fam>
-static int pair_mchain(const T* x, int64_t xs, const T* params, int64_t ps, int64_t n_groups, int32_t S, int32_t i0, int32_t i1, int32_t n_layers,
-                       const typename Fam::CLayer* layers, const T* add, T* tile, T* out, int32_t* status, void* stream) {
-    if (!x || !tile || !out || !layers || n_layers < 1 || n_layers > JF_MAX_MCHAIN || xs < Fam::DIM || ps < 0) return JF_ERR_BADARG;
+static int grid_mchain(const T* x, int64_t xs, int64_t xgs, const T* params, int64_t ps, int64_t n_groups, int32_t J, int32_t N, int32_t i0, int32_t i1,
+                       int32_t n_layers, const typename Fam::CLayer* layers, T* tile, int32_t* status, void* stream) {
+    if (!x || !tile || !layers || n_layers < 1 || n_layers > JF_MAX_MCHAIN || xs < Fam::DIM || ps < 0) return JF_ERR_BADARG;
     PairDims pd{};
-    int rc = pair_dims(n_groups, S, i0, i1, pd);
+    int rc = pair_dims(n_groups, J, N, xgs, i0, i1, pd);
     if (rc != JF_OK) return rc;
     MPairArgs<T, typename Fam::CLayer> a{};
     a.x = x; a.xs = xs; a.params = params; a.ps = ps; a.n_layers = n_layers; a.dim = Fam::DIM; a.status = status;
@@ -433,28 +456,46 @@ static int pair_mchain(const T* x, int64_t xs, const T* params, int64_t ps, int6
     if (n_groups == 0 || pd.ni == 0) return JF_OK;
     auto k = pair_mchain_kernel<T, Fam>;
     if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    const int64_t n_rows = n_groups * S, n_tiles = (pd.ni + 63) / 64;
+    const int64_t n_rows = n_groups * J, n_tiles = (pd.ni + 63) / 64;
     hipStream_t st = (hipStream_t)stream;
     jf::launch(k, dim3((unsigned)n_rows, pair_grid_y(n_rows, n_tiles)), dim3(64), lds, st, a, pd, tile);
-    rc = check_launch();
-    if (rc != JF_OK) return rc;
-    return pair_reduce<T>(tile, add, n_groups, pd, out, st);
+    return check_launch();
 }
 
 template <typename T>
-static int pair_mchain_any(int32_t fam, const T* x, int64_t xs, const T* p, int64_t ps, int64_t n_groups, int32_t S, int32_t i0, int32_t i1, int32_t n,
-                           const void* L, const T* add, T* tile, T* out, int32_t* status, void* stream) {
+static int grid_mchain_any(int32_t fam, const T* x, int64_t xs, int64_t xgs, const T* p, int64_t ps, int64_t n_groups, int32_t J, int32_t N, int32_t i0,
+                           int32_t i1, int32_t n, const void* L, T* tile, int32_t* status, void* stream) {
     switch (fam) {
-        case 'r': return pair_mchain<T, RFam>(x, xs, p, ps, n_groups, S, i0, i1, n, static_cast<const jf_r_layer*>(L), add, tile, out, status, stream);
-        case 'o': return pair_mchain<T, OFam>(x, xs, p, ps, n_groups, S, i0, i1, n, static_cast<const jf_o_layer*>(L), add, tile, out, status, stream);
-        case 'm': return pair_mchain<T, MFam>(x, xs, p, ps, n_groups, S, i0, i1, n, static_cast<const jf_m_layer*>(L), add, tile, out, status, stream);
-        case 'f': return pair_mchain<T, FFam>(x, xs, p, ps, n_groups, S, i0, i1, n, static_cast<const jf_f_layer*>(L), add, tile, out, status, stream);
+        case 'r': return grid_mchain<T, RFam>(x, xs, xgs, p, ps, n_groups, J, N, i0, i1, n, static_cast<const jf_r_layer*>(L), tile, status, stream);
+        case 'o': return grid_mchain<T, OFam>(x, xs, xgs, p, ps, n_groups, J, N, i0, i1, n, static_cast<const jf_o_layer*>(L), tile, status, stream);
+        case 'm': return grid_mchain<T, MFam>(x, xs, xgs, p, ps, n_groups, J, N, i0, i1, n, static_cast<const jf_m_layer*>(L), tile, status, stream);
+        case 'f': return grid_mchain<T, FFam>(x, xs, xgs, p, ps, n_groups, J, N, i0, i1, n, static_cast<const jf_f_layer*>(L), tile, status, stream);
         case 'v':
             // the reference asserts float64 for 'v' (exponential_map_s2.py:450, 493): no float32 kernel, as for jf_v_chain_*
-            if constexpr (sizeof(T) == 8) return pair_mchain<T, VFam>(x, xs, p, ps, n_groups, S, i0, i1, n, static_cast<const jf_v_layer*>(L), add, tile, out, status, stream);
+            if constexpr (sizeof(T) == 8) return grid_mchain<T, VFam>(x, xs, xgs, p, ps, n_groups, J, N, i0, i1, n, static_cast<const jf_v_layer*>(L), tile, status, stream);
             else return JF_ERR_UNSUPPORTED;
         default: return JF_ERR_UNSUPPORTED;
     }
+}
+
+// the pairwise entry point: the square case J = N = S of grid_mchain with per-group targets, reduced over j with uniform weights
+template <typename T>
+static int pair_mchain_any(int32_t fam, const T* x, int64_t xs, const T* p, int64_t ps, int64_t n_groups, int32_t S, int32_t i0, int32_t i1, int32_t n,
+                           const void* L, const T* add, T* tile, T* out, int32_t* status, void* stream) {
+    const bool known = fam == 'r' || fam == 'o' || fam == 'm' || fam == 'f' || (fam == 'v' && sizeof(T) == 8);
+    if (known && !out) return JF_ERR_BADARG;
+    const int rc = grid_mchain_any<T>(fam, x, xs, S, p, ps, n_groups, S, S, i0, i1, n, L, tile, status, stream);
+    if (rc != JF_OK || n_groups == 0 || i1 == i0) return rc;
+    return pair_reduce<T>(tile, nullptr, add, n_groups, S, i1 - i0, S, i0, out, (hipStream_t)stream);
+}
+
+template <typename T>
+static int grid_reduce(const T* tile, const T* logw, const T* add, int64_t n_groups, int32_t J, int32_t ni, T* out, void* stream) {
+    if (!tile || !out || n_groups < 0 || J < 1 || ni < 0) return JF_ERR_BADARG;
+    if (n_groups > (int64_t)0x7fffffff || n_groups * (int64_t)J > (int64_t)0x7fffffff || n_groups * (int64_t)ni > (int64_t)0x7fffffff * 256)
+        return JF_ERR_UNSUPPORTED;                        // (the limit of jf_grid_gf / jf_grid_mchain on the tile; one thread per (g, i): grid.x)
+    if (n_groups == 0 || ni == 0) return JF_OK;
+    return pair_reduce<T>(tile, logw, add, n_groups, J, ni, ni, 0, out, (hipStream_t)stream);
 }
 
 }  // namespace jf
@@ -475,5 +516,27 @@ int jf_pair_mchain_f32(int32_t fam, const float* x, int64_t xs, const float* p, 
 int jf_pair_mchain_f64(int32_t fam, const double* x, int64_t xs, const double* p, int64_t ps, int64_t n_groups, int32_t S, int32_t i0, int32_t i1,
                        int32_t n, const void* L, const double* add, double* tile, double* out, int32_t* st, void* s) {
     return jf::pair_mchain_any<double>(fam, x, xs, p, ps, n_groups, S, i0, i1, n, L, add, tile, out, st, s);
+}
+int jf_grid_gf_f32(const float* x, int64_t xs, int64_t xgs, const float* p, int64_t ps, int64_t n_groups, int32_t J, int32_t N, int32_t i0, int32_t i1,
+                   int32_t D, int32_t n, const jf_gf_layer* L, float* tile, int32_t* st, void* s) {
+    return jf::grid_gf<float>(x, xs, xgs, p, ps, n_groups, J, N, i0, i1, D, n, L, tile, st, s);
+}
+int jf_grid_gf_f64(const double* x, int64_t xs, int64_t xgs, const double* p, int64_t ps, int64_t n_groups, int32_t J, int32_t N, int32_t i0, int32_t i1,
+                   int32_t D, int32_t n, const jf_gf_layer* L, double* tile, int32_t* st, void* s) {
+    return jf::grid_gf<double>(x, xs, xgs, p, ps, n_groups, J, N, i0, i1, D, n, L, tile, st, s);
+}
+int jf_grid_mchain_f32(int32_t fam, const float* x, int64_t xs, int64_t xgs, const float* p, int64_t ps, int64_t n_groups, int32_t J, int32_t N,
+                       int32_t i0, int32_t i1, int32_t n, const void* L, float* tile, int32_t* st, void* s) {
+    return jf::grid_mchain_any<float>(fam, x, xs, xgs, p, ps, n_groups, J, N, i0, i1, n, L, tile, st, s);
+}
+int jf_grid_mchain_f64(int32_t fam, const double* x, int64_t xs, int64_t xgs, const double* p, int64_t ps, int64_t n_groups, int32_t J, int32_t N,
+                       int32_t i0, int32_t i1, int32_t n, const void* L, double* tile, int32_t* st, void* s) {
+    return jf::grid_mchain_any<double>(fam, x, xs, xgs, p, ps, n_groups, J, N, i0, i1, n, L, tile, st, s);
+}
+int jf_grid_reduce_f32(const float* tile, const float* logw, const float* add, int64_t n_groups, int32_t J, int32_t ni, float* out, void* s) {
+    return jf::grid_reduce<float>(tile, logw, add, n_groups, J, ni, out, s);
+}
+int jf_grid_reduce_f64(const double* tile, const double* logw, const double* add, int64_t n_groups, int32_t J, int32_t ni, double* out, void* s) {
+    return jf::grid_reduce<double>(tile, logw, add, n_groups, J, ni, out, s);
 }
 }

@@ -1831,24 +1831,24 @@ class pdf(nn.Module):
                     out[sm] = _hip.segment_reduce(lp, S, "neg_mean")
         return out
 
-    def _kernel_pair_logp(self, sm, xdef, add, data_summary, batch, S, iterative_samplesize, max_iterative_batchsize, status):
-        """log p_k(x_k of sample i) for the marginal of sub-manifold sm > 0, one value per sample: the conditional density of block sm averaged
-        (log-mean-exp) over the S draws of x_<sm of the same conditional input.  The amortisation MLP of block sm sees (cond_g, embed(x_<sm of
-        sample j)) only, so its rows are computed ONCE on batch * S rows and the S x S evaluation is one pairwise launch per (group chunk,
-        i-range) (_hip.pair_logmeanexp): blocks other than sm are not evaluated at all.  None: the pair kernels decline this block (the caller
-        takes _generic_pair_logp)."""
+    def _pair_plan(self, sm, dtype):
+        """(kind, layers as the launch takes them, parameters per row) of block sm for the pair / grid kernels (_hip.pair_logmeanexp,
+        _hip.grid_logp), or None: this block is outside them (the library may still decline a chain it is handed)."""
         layers = list(self.layer_list[sm])
         kind = self.pdf_defs_list[sm][0]
-        a, b = self.target_dim_indices[sm]
         if self.amortize_everything:
             return None
         fam = _manifold_family(layers)
         if kind == "e" and gfl.chain_supported(layers):
-            plan = ("g", _hip.gf_layer_array([l.c_struct() for l in layers]), sum(l.total_param_num for l in layers))
-        elif fam is not None and not (fam == "v" and xdef.dtype != torch.float64):
-            plan = (fam, _mchain_structs(fam, layers), sum(l.total_param_num for l in layers))
-        else:
-            return None
+            return ("g", _hip.gf_layer_array([l.c_struct() for l in layers]), sum(l.total_param_num for l in layers))
+        if fam is not None and not (fam == "v" and dtype != torch.float64):
+            return (fam, _mchain_structs(fam, layers), sum(l.total_param_num for l in layers))
+        return None
+
+    def _pair_param_rows(self, sm, plan, xdef, data_summary):
+        """the parameter rows of block sm for the rows of xdef (default coordinates; only the columns of the blocks before sm are read) and
+        their conditional input: the amortisation MLP once per row, or the block's one permanent row (1, P)."""
+        layers = list(self.layer_list[sm])
         embeds = self._conditioning_rows(xdef, data_summary)
         if embeds is None:
             embeds = [self.layer_list[p][-1]._embedding_conditional_return(xdef[:, self.target_dim_indices[p][0]:self.target_dim_indices[p][1]])
@@ -1860,6 +1860,19 @@ class pdf(nn.Module):
             else:
                 rows = [l._params_for(xdef, None) for l in layers]
                 extra = torch.cat(rows, dim=1) if len(rows) > 1 else rows[0]
+        return extra
+
+    def _kernel_pair_logp(self, sm, xdef, add, data_summary, batch, S, iterative_samplesize, max_iterative_batchsize, status):
+        """log p_k(x_k of sample i) for the marginal of sub-manifold sm > 0, one value per sample: the conditional density of block sm averaged
+        (log-mean-exp) over the S draws of x_<sm of the same conditional input.  The amortisation MLP of block sm sees (cond_g, embed(x_<sm of
+        sample j)) only, so its rows are computed ONCE on batch * S rows and the S x S evaluation is one pairwise launch per (group chunk,
+        i-range) (_hip.pair_logmeanexp): blocks other than sm are not evaluated at all.  None: the pair kernels decline this block (the caller
+        takes _generic_pair_logp)."""
+        a, b = self.target_dim_indices[sm]
+        plan = self._pair_plan(sm, xdef.dtype)
+        if plan is None:
+            return None
+        extra = self._pair_param_rows(sm, plan, xdef, data_summary)
         tgt_c = xdef[:, a:b].contiguous()
         out = torch.empty((batch * S,), dtype=xdef.dtype, device=xdef.device)
         for g0 in range(0, batch, max_iterative_batchsize):
@@ -2039,6 +2052,213 @@ class pdf(nn.Module):
             for i, f in enumerate(previous_flags):
                 self.set_embedding_flags(f, sub_pdf_index=i)
         return ret
+
+    # =========================================================================================== densities on product grids / marginals
+    def _target_coordinates(self, force_embedding_coordinates, force_intrinsic_coordinates):
+        """-> (name of the coordinate system the flags select, the width of every sub-manifold's targets in it)"""
+        if force_embedding_coordinates:
+            return "embedding", self.target_dims_embedded
+        if force_intrinsic_coordinates:
+            return "intrinsic", self.target_dims_intrinsic
+        return "default", self.target_dims
+
+    def _rect_block_logp(self, k, xdef, cond, tdef, shared, G, J, N, reduce, add, group_chunk, max_tile_elements, status):
+        """the conditional density of block k for J prefix rows against N targets per group (G groups = conditional inputs):
+
+            tile[g, j, i] = log p_k(tdef[g, i] | cond[g], x_<k = xdef[g * J + j])
+
+        xdef (G * J, total_target_dim): prefix rows in default coordinates (the columns of block k and later are not read); cond (G, .) or
+        None; tdef (N, w) when `shared`, else (G * N, w): block k's targets in default coordinates.  reduce = False -> the tile (G, J, N);
+        reduce = True -> (G, N), the log-mean-exp over j in the fixed order 0 .. J-1, plus add (G * N,) (or (N,) when shared; None = 0).
+        The parameter rows of block k are computed once on the G * J prefix rows; then one _hip.grid_logp launch per chunk of (groups,
+        target range), no scratch tile larger than max_tile_elements.  A value depends on its own target and parameter row only, so the
+        chunking does not change a bit.  Blocks the kernels decline go through the ordinary kernels row by row (_generic_rect_logp)."""
+        dt, dev = tdef.dtype, tdef.device
+        w = tdef.shape[1]
+        out = torch.empty((G, N) if reduce else (G, J, N), dtype=dt, device=dev)
+        ds = None
+        if cond is not None:
+            def rep(c):
+                return c.repeat_interleave(J, dim=0) if J > 1 else c
+            ds = [rep(c) for c in cond] if type(cond) == list else rep(cond)
+        plan = self._pair_plan(k, dt)
+        extra = None if plan is None else self._pair_param_rows(k, plan, xdef, ds)
+        tdef = tdef.contiguous()
+        add2 = None
+        if add is not None:
+            add2 = (add.reshape(1, N).expand(G, N) if shared else add.reshape(G, N)).contiguous()
+        if plan is not None:
+            permanent = extra.shape[0] == 1 and G * J != 1
+            # without a reduction over j and with shared targets every prefix row may be a group of its own: any row range is one launch
+            flat = shared and not reduce
+            n_rows, per_row = (G * J, 1) if flat else (G, J)
+            step = max(1, min(n_rows, group_chunk if not flat else n_rows, max_tile_elements // max(per_row, 1)))
+            declined = False
+            for r0 in range(0, n_rows, step):
+                r1 = min(n_rows, r0 + step)
+                ni_max = max(1, max_tile_elements // ((r1 - r0) * per_row))
+                prow = extra if permanent else extra[r0 * per_row:r1 * per_row]
+                x_c = tdef if shared else tdef[r0 * N:r1 * N]
+                for i0 in range(0, N, ni_max):
+                    i1 = min(N, i0 + ni_max)
+                    tile = _hip.grid_logp(plan[0], x_c, prow, plan[2], r1 - r0, per_row, N, plan[1], w, i0=i0, i1=i1, shared_targets=shared,
+                                          status=status)
+                    if tile is None:                      # the library declines this chain: every launch would
+                        declined = True
+                        break
+                    if reduce:
+                        out[r0:r1, i0:i1] = _hip.grid_reduce(tile, add=None if add2 is None else add2[r0:r1, i0:i1])
+                    else:
+                        out.reshape(n_rows, per_row, N)[r0:r1, :, i0:i1] = tile
+                if declined:
+                    break
+            if not declined:
+                return out
+        return self._generic_rect_logp(k, xdef, cond, tdef, shared, G, J, N, reduce, add2, group_chunk, max_tile_elements, status, out)
+
+    def _generic_rect_logp(self, k, xdef, cond, tdef, shared, G, J, N, reduce, add2, group_chunk, max_tile_elements, status, out):
+        """the values of _rect_block_logp on the ordinary kernels, for any block (the scheme of _generic_pair_logp): per chunk of (conditional
+        inputs, targets) the rows (g, i, j) = (x_<k of prefix j, target i) go through the log-prob direction up to block k."""
+        a, b = self.target_dim_indices[k]
+        ba, bb = self.base_dim_indices[k]
+        total = self.total_target_dim
+        pre = xdef.reshape(G, J, -1)
+        tg = tdef.reshape(1 if shared else G, N, b - a)
+        budget = min(max_tile_elements, 1 << 20)          # rows of full width per pass
+        gstep = max(1, min(G, group_chunk, budget // max(J, 1)))
+        for g0 in range(0, G, gstep):
+            g1 = min(G, g0 + gstep)
+            nb = g1 - g0
+            ni_max = max(1, budget // (nb * J))
+            for i0 in range(0, N, ni_max):
+                i1 = min(N, i0 + ni_max)
+                ni = i1 - i0
+                prev = pre[g0:g1, None, :, :a].expand(nb, ni, J, a)
+                fin = (tg[:, i0:i1] if shared else tg[g0:g1, i0:i1])[:, :, None, :].expand(nb, ni, J, b - a)
+                fill = torch.ones((nb, ni, J, total - b), dtype=tdef.dtype, device=tdef.device)
+                filled = torch.cat([prev, fin, fill], dim=3).reshape(nb * ni * J, total)
+                ds2 = None
+                if cond is not None:
+                    def rep(c):
+                        return c[g0:g1].repeat_interleave(ni * J, dim=0)
+                    ds2 = [rep(c) for c in cond] if type(cond) == list else rep(cond)
+                marks = []
+                base = self._inverse_impl(filled, None, ds2, None, False, False, False, False, status, per_block=marks, last_block=k)[0]
+                flow = _block_log_dets(marks, len(self.layer_list), False, False)[0]
+                lp = _hip.normal_logp(base[:, ba:bb]) + flow[k]
+                if reduce:
+                    red = _hip.segment_reduce(lp, J, "logmeanexp").reshape(nb, ni)
+                    out[g0:g1, i0:i1] = red if add2 is None else add2[g0:g1, i0:i1] + red
+                else:
+                    out[g0:g1, :, i0:i1] = lp.reshape(nb, ni, J).transpose(1, 2)
+        return out
+
+    def log_prob_on_grid(self, axes, conditional_input=None, force_embedding_coordinates=False, force_intrinsic_coordinates=False,
+                         return_blocks=False, max_tile_elements=2**26):
+        """log p on the product grid axes_0 x axes_1 x ... for every conditional input -> (C, N_0, ..., N_{n-1}) (C = 1 when unconditional).
+        `axes`: one (N_k, d_k) tensor per sub-pdf, in the coordinates the flags select (default coordinates otherwise), shared by all
+        conditional inputs.  With return_blocks also the list of factors lp_k of shape (C, N_0, ..., N_k) = log p_k(x_k | c, x_<k): the result
+        is their broadcast sum, added in the order k = 0, 1, ...
+
+        The parameters of block k depend on the conditional input and on x_<k only, so the amortisation MLP of block k runs on the
+        C * N_0 * ... * N_{k-1} prefix rows of the grid -- not on the C * N_0 * ... * N_{n-1} rows of the mesh -- and a rectangular pair kernel
+        (csrc/pair_kernels.hip, _hip.grid_logp) evaluates the N_k points of axis k against each of those rows: one workgroup per parameter
+        row.  Coordinate changes are applied to each axis once.  Nothing of the size of the mesh times a row width exists; scratch tiles stay
+        below max_tile_elements values (the result does not depend on it).  Blocks the kernels decline take the ordinary kernels, chunked."""
+        nsub = len(self.layer_list)
+        if not isinstance(axes, (list, tuple)) or len(axes) != nsub:
+            raise ValueError("log_prob_on_grid: expected one axis per sub-pdf (%d), got %s" % (nsub, len(axes) if isinstance(axes, (list, tuple)) else type(axes)))
+        coords, dims = self._target_coordinates(force_embedding_coordinates, force_intrinsic_coordinates)
+        for k, ax in enumerate(axes):
+            if ax.dim() != 2 or ax.shape[1] != dims[k] or ax.shape[0] < 1:
+                raise ValueError("log_prob_on_grid: axis %d must be a (N, %d) tensor in %s coordinates, got shape %s" % (k, dims[k], coords, tuple(ax.shape)))
+        if max_tile_elements < 1:
+            raise ValueError("log_prob_on_grid: max_tile_elements must be positive")
+        _, _, C, cond = self._repeat_conditional(conditional_input, 1, None, None)
+        _hip.require_device(*axes)
+        blocks = []
+        with torch.no_grad():
+            status = _hip.new_status(axes[0].device) if self.check_status else None
+            axdef, chart = [], []
+            for k, ax in enumerate(axes):                 # each axis to default coordinates once; its chart log-det belongs to block k
+                t, ld = ax, None
+                if coords != "default":
+                    t, ld = self.layer_list[k][-1].transform_target_space(ax, log_det=None, transform_from=coords, transform_to="default")
+                axdef.append(t.contiguous())
+                chart.append(ld if isinstance(ld, torch.Tensor) else None)
+            J = 1
+            for k in range(nsub):
+                N = axdef[k].shape[0]
+                # prefix rows (c, a_0, ..., a_{k-1}) in default coordinates; the columns of block k and later are never read
+                xdef = torch.zeros((C * J, self.total_target_dim), dtype=axdef[k].dtype, device=axdef[k].device)
+                shape = [C] + [axdef[p].shape[0] for p in range(k)]
+                for p in range(k):
+                    pa, pb = self.target_dim_indices[p]
+                    view = [1] * (k + 1) + [pb - pa]
+                    view[p + 1] = shape[p + 1]
+                    xdef.reshape(*shape, -1)[..., pa:pb] = axdef[p].reshape(view)
+                lp = self._rect_block_logp(k, xdef, cond, axdef[k], True, C, J, N, False, None, C, max_tile_elements, status)
+                lp = lp.reshape(*shape, N)
+                if chart[k] is not None:
+                    lp = lp + chart[k]
+                blocks.append(lp)
+                J *= N
+            self._report_status(status)
+            total = blocks[0].reshape(list(blocks[0].shape) + [1] * (nsub - 1)) if nsub > 1 else blocks[0]
+            for k in range(1, nsub):
+                total = total + blocks[k].reshape(list(blocks[k].shape) + [1] * (nsub - 1 - k))
+        return (total, blocks) if return_blocks else total
+
+    def marginal_log_prob(self, sub_manifold, targets, conditional_input=None, samplesize=100, force_embedding_coordinates=False,
+                          force_intrinsic_coordinates=False, max_iterative_batchsize=20, max_tile_elements=2**26, predefined_base=None,
+                          return_samples=False):
+        """log-density of the marginal of sub-manifold `sub_manifold` at arbitrary targets -> (C, N) (C = 1 when unconditional).  `targets`:
+        (N, d_k), shared by all conditional inputs, or (C, N, d_k), in the coordinates the flags select (default coordinates otherwise).
+        Sub-manifold 0 is exact: block 0 depends on the conditional input alone.  For k > 0 it is the Monte-Carlo estimate
+
+            log p_k(x | c) = log 1/S sum_j p_k(x | c, x_<k of sample j)
+
+        over S = `samplesize` samples of the pdf per conditional input (drawn as entropy_iterative draws them; `predefined_base` injects
+        their standard-normal base samples): the parameter rows of block k are computed once on the C * S samples and a rectangular pair
+        kernel evaluates the N targets against the S rows of each conditional input (csrc/pair_kernels.hip), reduced over j in a fixed
+        order.  max_iterative_batchsize (conditional inputs per launch) and max_tile_elements (values per scratch tile) bound the memory and
+        do not change a bit of the result.  With return_samples also the (C * S, .) samples (None for sub-manifold 0)."""
+        nsub = len(self.layer_list)
+        k = sub_manifold
+        if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k < nsub:
+            raise ValueError("marginal_log_prob: sub_manifold must be an index in [0, %d), got %r" % (nsub, k))
+        coords, dims = self._target_coordinates(force_embedding_coordinates, force_intrinsic_coordinates)
+        if targets.dim() not in (2, 3) or targets.shape[-1] != dims[k]:
+            raise ValueError("marginal_log_prob: targets must be (N, %d) or (C, N, %d) in %s coordinates, got shape %s"
+                             % (dims[k], dims[k], coords, tuple(targets.shape)))
+        if samplesize < 1 or max_iterative_batchsize < 1 or max_tile_elements < 1:
+            raise ValueError("marginal_log_prob: samplesize, max_iterative_batchsize and max_tile_elements must be positive")
+        S = samplesize if k > 0 else 1
+        dt, dev, C, data_summary = self._repeat_conditional(conditional_input, S, None, None)
+        shared = targets.dim() == 2
+        if not shared and targets.shape[0] != C:
+            raise ValueError("marginal_log_prob: %d target sets for %d conditional inputs" % (targets.shape[0], C))
+        N = targets.shape[-2]
+        _hip.require_device(targets)
+        samples = None
+        with torch.no_grad():
+            t2, add = targets.reshape(-1, dims[k]), None
+            if coords != "default":
+                t2, add = self.layer_list[k][-1].transform_target_space(t2, log_det=None, transform_from=coords, transform_to="default")
+                add = add if isinstance(add, torch.Tensor) else None
+            if k == 0:
+                status = _hip.new_status(targets.device) if self.check_status else None
+                xdef = torch.zeros((C, self.total_target_dim), dtype=t2.dtype, device=t2.device)
+            else:
+                samples, _, status = self._sampling_pass(predefined_base, S * C, dt, dev, data_summary, force_embedding_coordinates,
+                                                         force_intrinsic_coordinates, [])
+                xdef = samples
+                if coords != "default":
+                    xdef, _ = self.transform_target_space(samples, None, transform_from=coords, transform_to="default")
+            out = self._rect_block_logp(k, xdef, conditional_input, t2, shared, C, S, N, True, add, max_iterative_batchsize, max_tile_elements,
+                                        status)
+            self._report_status(status)
+        return (out, samples) if return_samples else out
 
     def _first_marginal_logp(self, x0, data_summary):
         """log-pdf of the first sub-manifold's marginal at x0 (embedding coordinates): block 0 depends on the conditional input alone, so the
