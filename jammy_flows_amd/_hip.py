@@ -263,6 +263,20 @@ for _fam, _cls in MCHAIN_LAYER_TYPES.items():
                                                  _P, _P]
 
 
+# name -> (argtypes, restype): the analysis reductions of include/jammy_hip_analysis.h (a header and an ABI number of their own, so not part of
+# exported_symbols()).  Bound on first use by _analysis(), not by lib().
+_D = ctypes.POINTER(ctypes.c_double)
+_SIGNATURES_ANALYSIS = {"jf_analysis_abi_version": ([], ctypes.c_int), "jf_hpd_scratch_bytes": ([_I64, _I64, _I32], _I64)}
+for _d in ("_f32", "_f64"):
+    #                                        lp  stride logw G     M
+    _SIGNATURES_ANALYSIS["jf_hpd_stats" + _d] = ([_P, _I64, _P, _I64, _I64, _P, _P, _P, _P, _I64, _P], ctypes.c_int)
+    _SIGNATURES_ANALYSIS["jf_hpd_mass" + _d] = ([_P, _I64, _P, _I64, _I64, _P, _I32, _P, _P, _P, _I64, _P], ctypes.c_int)
+    _SIGNATURES_ANALYSIS["jf_hpd_levels" + _d] = ([_P, _I64, _P, _I64, _I64, _D, _I32, _P, _P, _P, _P, _I64, _P], ctypes.c_int)
+JF_ANALYSIS_ABI = 1
+HPD_CHUNK = 4096                 # JF_HPD_CHUNK: cells of a tile row that one workgroup reduces (csrc/hpd_kernels.hip)
+_analysis_bound = False
+
+
 def exported_symbols():
     """all symbols include/jammy_hip.h declares (used by the CPU-side ABI test)."""
     names = ["jf_abi_version"]
@@ -297,6 +311,27 @@ def lib():
     if NEWTON_RULE == "reference" and int(l.jf_get_newton_rule()) != 1:
         raise HipUnavailable("JF_NEWTON_RULE=reference, but %s was not built with the reference's solver rule" % LIB_PATH)
     return _lib
+
+
+def _analysis():
+    """the library with the entry points of include/jammy_hip_analysis.h bound (once, on first use); a library built before they existed
+    raises HipUnavailable with the rebuild hint."""
+    global _analysis_bound
+    l = lib()
+    if _analysis_bound:
+        return l
+    for name, (argtypes, restype) in _SIGNATURES_ANALYSIS.items():
+        fn = getattr(l, name, None)
+        if fn is None:
+            raise HipUnavailable("%s does not export %s (include/jammy_hip_analysis.h): it is older than this package -- rebuild it with "
+                                 "`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C jammy_flows_amd/csrc`)" % (LIB_PATH, name))
+        fn.argtypes = argtypes
+        fn.restype = restype
+    if int(l.jf_analysis_abi_version()) != JF_ANALYSIS_ABI:
+        raise HipUnavailable("%s has analysis ABI %d, this package needs %d -- rebuild it with `python -c 'import __graft_entry__ as g; g.build()'`"
+                             % (LIB_PATH, int(l.jf_analysis_abi_version()), JF_ANALYSIS_ABI))
+    _analysis_bound = True
+    return l
 
 
 def get_newton_rule():
@@ -1687,6 +1722,86 @@ def grid_reduce(tile, logw=None, add=None):
     out = torch.empty((G, ni), dtype=tile.dtype, device=tile.device)
     _launch("jf_grid_reduce" + _suffix(tile), "", (_ptr(tile), _ptr(logw), _ptr(add), G, J, ni, _ptr(out)), dev)
     return out
+
+
+def _hpd_tile(what, tile, logw, log_norm=None):
+    """the arguments every HPD reduction shares: tile (G, M), unit stride inside a row; logw (M,) of the tile's dtype or None; log_norm (G,)
+    float64 -> (device, tile, logw, log_norm) as the entry points take them"""
+    dev = require_device(tile, logw, log_norm)
+    if tile.dim() != 2 or tile.shape[1] < 1:
+        raise ValueError("%s: expected a (G, M) tile with M >= 1, got shape %s" % (what, tuple(tile.shape)))
+    _suffix(tile)
+    if tile.stride(1) != 1 or (tile.shape[0] > 1 and tile.stride(0) < tile.shape[1]):
+        tile = tile.contiguous()
+    if logw is not None:
+        if logw.dtype != tile.dtype or tuple(logw.shape) != (tile.shape[1],):
+            raise ValueError("%s: logw must be a (M,) = (%d,) tensor of the tile's dtype" % (what, tile.shape[1]))
+        logw = logw.contiguous()
+    if log_norm is not None:
+        if log_norm.dtype != torch.float64 or tuple(log_norm.shape) != (tile.shape[0],):
+            raise ValueError("%s: log_norm must be the (G,) float64 tensor of hpd_stats" % what)
+        log_norm = log_norm.contiguous()
+    return dev, tile, logw, log_norm
+
+
+def _hpd_scratch(what, tile, T):
+    G, M = tile.shape
+    n = int(_analysis().jf_hpd_scratch_bytes(G, M, T))
+    if n < 0:
+        _check(n, "%s (a tile of %d x %d, %d thresholds)" % (what, G, M, T))
+    return torch.empty(n // 8, dtype=torch.int64, device=tile.device), n
+
+
+def _hpd_row_stride(tile):
+    return tile.stride(0) if tile.shape[0] > 1 else max(tile.stride(0), tile.shape[1])
+
+
+def hpd_stats(tile, logw=None):
+    """tile (G, M) of log-densities, logw (M,) cell log-volumes or None -> (log_norm (G,) float64 = log sum_m exp(tile + logw), max_lp (G,) of the
+    tile's dtype, argmax (G,) int64: the first index of the row's maximum) (jf_hpd_stats).  Rows holding a NaN or +inf: NaN, NaN, -1."""
+    dev, tile, logw, _ = _hpd_tile("hpd_stats", tile, logw)
+    G, M = tile.shape
+    log_norm = torch.empty(G, dtype=torch.float64, device=tile.device)
+    max_lp = torch.empty(G, dtype=tile.dtype, device=tile.device)
+    argmax = torch.empty(G, dtype=torch.int64, device=tile.device)
+    scratch, nbytes = _hpd_scratch("hpd_stats", tile, 0)
+    _launch("jf_hpd_stats" + _suffix(tile), "hpd", (_ptr(tile), _hpd_row_stride(tile), _ptr(logw), G, M, _ptr(log_norm), _ptr(max_lp), _ptr(argmax),
+                                                   _ptr(scratch), nbytes), dev)
+    return log_norm, max_lp, argmax
+
+
+def hpd_mass(tile, thr, log_norm, logw=None):
+    """mass (G, T) float64: mass[g, t] = sum over the cells with tile[g, m] >= thr[g, t] of exp(tile[g, m] + logw[m] - log_norm[g]), in [0, 1]
+    (jf_hpd_mass).  thr (G, T) of the tile's dtype; log_norm from hpd_stats of the same tile and logw."""
+    dev, tile, logw, log_norm = _hpd_tile("hpd_mass", tile, logw, log_norm)
+    require_device(tile, thr)
+    G, M = tile.shape
+    if thr.dim() != 2 or thr.shape[0] != G or thr.dtype != tile.dtype:
+        raise ValueError("hpd_mass: thr must be a (G, T) = (%d, T) tensor of the tile's dtype, got %s %s" % (G, tuple(thr.shape), thr.dtype))
+    thr = thr.contiguous()
+    T = thr.shape[1]
+    mass = torch.empty((G, T), dtype=torch.float64, device=tile.device)
+    scratch, nbytes = _hpd_scratch("hpd_mass", tile, T)
+    _launch("jf_hpd_mass" + _suffix(tile), "hpd", (_ptr(tile), _hpd_row_stride(tile), _ptr(logw), G, M, _ptr(thr), T, _ptr(log_norm), _ptr(mass),
+                                                  _ptr(scratch), nbytes), dev)
+    return mass
+
+
+def hpd_levels(tile, q, log_norm, logw=None):
+    """(level (G, Q) of the tile's dtype, level_mass (G, Q) float64): level[g, j] = the largest of the row's own values t with
+    mass(tile[g] >= t) >= q[j], and the mass it reaches (jf_hpd_levels).  q: host numbers in (0, 1)."""
+    dev, tile, logw, log_norm = _hpd_tile("hpd_levels", tile, logw, log_norm)
+    G, M = tile.shape
+    qs = [float(v) for v in (q.tolist() if hasattr(q, "tolist") else q)]
+    if not qs or not all(0.0 < v < 1.0 for v in qs):
+        raise ValueError("hpd_levels: credible masses must be a non-empty sequence of numbers in (0, 1), got %s" % (qs,))
+    Q = len(qs)
+    level = torch.empty((G, Q), dtype=tile.dtype, device=tile.device)
+    level_mass = torch.empty((G, Q), dtype=torch.float64, device=tile.device)
+    scratch, nbytes = _hpd_scratch("hpd_levels", tile, Q)
+    _launch("jf_hpd_levels" + _suffix(tile), "hpd", (_ptr(tile), _hpd_row_stride(tile), _ptr(logw), G, M, (ctypes.c_double * Q)(*qs), Q, _ptr(log_norm),
+                                                    _ptr(level), _ptr(level_mass), _ptr(scratch), nbytes), dev)
+    return level, level_mass
 
 
 def amlp_stage(x, seg, n_in, n_out, rank, has_bias, act, residual=None):

@@ -2153,6 +2153,19 @@ class pdf(nn.Module):
                     out[g0:g1, :, i0:i1] = lp.reshape(nb, ni, J).transpose(1, 2)
         return out
 
+    def _check_grid_axes(self, what, axes, force_embedding_coordinates, force_intrinsic_coordinates, max_tile_elements):
+        """the argument checks of the product-grid methods, before anything touches a device -> (coordinate system, width of every axis)"""
+        nsub = len(self.layer_list)
+        if not isinstance(axes, (list, tuple)) or len(axes) != nsub:
+            raise ValueError("%s: expected one axis per sub-pdf (%d), got %s" % (what, nsub, len(axes) if isinstance(axes, (list, tuple)) else type(axes)))
+        coords, dims = self._target_coordinates(force_embedding_coordinates, force_intrinsic_coordinates)
+        for k, ax in enumerate(axes):
+            if ax.dim() != 2 or ax.shape[1] != dims[k] or ax.shape[0] < 1:
+                raise ValueError("%s: axis %d must be a (N, %d) tensor in %s coordinates, got shape %s" % (what, k, dims[k], coords, tuple(ax.shape)))
+        if max_tile_elements < 1:
+            raise ValueError("%s: max_tile_elements must be positive" % what)
+        return coords, dims
+
     def log_prob_on_grid(self, axes, conditional_input=None, force_embedding_coordinates=False, force_intrinsic_coordinates=False,
                          return_blocks=False, max_tile_elements=2**26):
         """log p on the product grid axes_0 x axes_1 x ... for every conditional input -> (C, N_0, ..., N_{n-1}) (C = 1 when unconditional).
@@ -2166,14 +2179,7 @@ class pdf(nn.Module):
         row.  Coordinate changes are applied to each axis once.  Nothing of the size of the mesh times a row width exists; scratch tiles stay
         below max_tile_elements values (the result does not depend on it).  Blocks the kernels decline take the ordinary kernels, chunked."""
         nsub = len(self.layer_list)
-        if not isinstance(axes, (list, tuple)) or len(axes) != nsub:
-            raise ValueError("log_prob_on_grid: expected one axis per sub-pdf (%d), got %s" % (nsub, len(axes) if isinstance(axes, (list, tuple)) else type(axes)))
-        coords, dims = self._target_coordinates(force_embedding_coordinates, force_intrinsic_coordinates)
-        for k, ax in enumerate(axes):
-            if ax.dim() != 2 or ax.shape[1] != dims[k] or ax.shape[0] < 1:
-                raise ValueError("log_prob_on_grid: axis %d must be a (N, %d) tensor in %s coordinates, got shape %s" % (k, dims[k], coords, tuple(ax.shape)))
-        if max_tile_elements < 1:
-            raise ValueError("log_prob_on_grid: max_tile_elements must be positive")
+        coords, dims = self._check_grid_axes("log_prob_on_grid", axes, force_embedding_coordinates, force_intrinsic_coordinates, max_tile_elements)
         _, _, C, cond = self._repeat_conditional(conditional_input, 1, None, None)
         _hip.require_device(*axes)
         blocks = []
@@ -2208,6 +2214,94 @@ class pdf(nn.Module):
             for k in range(1, nsub):
                 total = total + blocks[k].reshape(list(blocks[k].shape) + [1] * (nsub - 1 - k))
         return (total, blocks) if return_blocks else total
+
+    def hpd_on_grid(self, axes, labels=None, conditional_input=None, axis_log_volumes=None, credible_masses=None,
+                    force_embedding_coordinates=False, force_intrinsic_coordinates=False, max_tile_elements=2**26):
+        """what the reference's coverage_and_or_pdf_scan reduces its scan to (main/default.py:2162-2184, 2214-2237), on the product grid of
+        log_prob_on_grid and on the device: the grid's total mass, the MAP cell, the exact highest-posterior-density (HPD) coverage of labels
+        and the log-density levels of credible regions -> dict of device tensors (C = 1 when unconditional, n sub-pdfs, D target columns):
+
+            log_norm (C,) float64            log sum over the cells of exp(log p + log volume)
+            map_index (C, n) int64, map_positions (C, D), map_log_prob (C,)       the densest cell (first index among equals)
+          with labels (C, D), in the coordinates of the axes:
+            label_index (C, n) int64         per axis the point nearest to the label (first index on ties): the reference's
+                                             argmin(norm(label - positions)), since the squared distance is the sum over the axes
+            label_log_prob (C,)              the tile's value there
+            coverage (C,) float64            mass of the cells at least as dense as the label's, over the grid's total mass -- the
+                                             reference's cumsum(sorted)[label], without a sort's tie order
+            real_cov_values (C,) float64     coverage * exp(log_norm): the reference's unnormalised value
+          with credible_masses (Q numbers in (0, 1)):
+            levels (C, Q)                    the largest tile value t with mass(log p >= t) >= q
+            level_masses (C, Q) float64      the mass it reaches
+
+        axes, the coordinate flags, conditional_input and max_tile_elements: as in log_prob_on_grid, which evaluates the tile.
+        axis_log_volumes: None, or per axis None or a (N_k,) tensor of log-volumes; a cell's log-volume is their sum.  The reductions are
+        csrc/hpd_kernels.hip (_hip.hpd_stats / hpd_mass / hpd_levels): double arithmetic for both dtypes, fixed order, so a conditional
+        input's results do not depend on the others in the batch.  ValueError when a log_norm is not finite."""
+        coords, dims = self._check_grid_axes("hpd_on_grid", axes, force_embedding_coordinates, force_intrinsic_coordinates, max_tile_elements)
+        nsub = len(axes)
+        sizes = [ax.shape[0] for ax in axes]
+        vols = [None] * nsub if axis_log_volumes is None else axis_log_volumes
+        if not isinstance(vols, (list, tuple)) or len(vols) != nsub:
+            raise ValueError("hpd_on_grid: axis_log_volumes must be None or hold one entry per axis (%d)" % nsub)
+        for k, v in enumerate(vols):
+            if v is not None and tuple(v.shape) != (sizes[k],):
+                raise ValueError("hpd_on_grid: the log-volumes of axis %d must be a (%d,) tensor, got shape %s" % (k, sizes[k], tuple(v.shape)))
+        first = conditional_input[0] if type(conditional_input) == list else conditional_input
+        C = 1 if first is None else first.shape[0]
+        D = sum(dims)
+        if labels is not None and (labels.dim() != 2 or tuple(labels.shape) != (C, D)):
+            raise ValueError("hpd_on_grid: labels must be a (C, D) = (%d, %d) tensor in %s coordinates, one row per conditional input, got shape %s"
+                             % (C, D, coords, tuple(labels.shape)))
+        qs = None
+        if credible_masses is not None:
+            qs = [float(v) for v in (credible_masses.tolist() if hasattr(credible_masses, "tolist") else credible_masses)]
+            if not qs or not all(0.0 < v < 1.0 for v in qs):
+                raise ValueError("hpd_on_grid: credible_masses must be a non-empty sequence of numbers in (0, 1), got %s" % (qs,))
+        tile = self.log_prob_on_grid(axes, conditional_input=conditional_input, force_embedding_coordinates=force_embedding_coordinates,
+                                     force_intrinsic_coordinates=force_intrinsic_coordinates, max_tile_elements=max_tile_elements)
+        _hip.require_device(tile, labels, *[v for v in vols if v is not None])
+        with torch.no_grad():
+            lp = tile.reshape(C, -1)
+            logw = None
+            if any(v is not None for v in vols):
+                logw = torch.zeros(sizes, dtype=tile.dtype, device=tile.device)
+                for k, v in enumerate(vols):
+                    if v is not None:
+                        logw = logw + v.to(tile.dtype).reshape([sizes[k] if p == k else 1 for p in range(nsub)])
+                logw = logw.reshape(-1)
+
+            def cells(flat):                              # flat cell index (C,) -> per-axis indices (C, n), row-major as the tile
+                idx = []
+                for n_k in reversed(sizes):
+                    idx.append(flat % n_k)
+                    flat = torch.div(flat, n_k, rounding_mode="floor")
+                return torch.stack(idx[::-1], dim=1)
+
+            log_norm, max_lp, argmax = _hip.hpd_stats(lp, logw)
+            map_index = cells(argmax.clamp(min=0))
+            ret = {"log_norm": log_norm, "map_index": map_index, "map_log_prob": max_lp,
+                   "map_positions": torch.cat([ax[map_index[:, k]] for k, ax in enumerate(axes)], dim=1)}
+            if labels is not None:
+                idx, a = [], 0
+                for k, ax in enumerate(axes):
+                    d2 = ((labels[:, None, a:a + dims[k]] - ax[None]) ** 2).sum(dim=2)
+                    idx.append(torch.argmin(d2, dim=1))
+                    a += dims[k]
+                label_index = torch.stack(idx, dim=1)
+                flat = torch.zeros(C, dtype=torch.int64, device=tile.device)
+                for k in range(nsub):
+                    flat = flat * sizes[k] + label_index[:, k]
+                label_lp = lp.gather(1, flat[:, None])
+                coverage = _hip.hpd_mass(lp, label_lp, log_norm, logw)[:, 0]
+                ret.update(label_index=label_index, label_log_prob=label_lp[:, 0], coverage=coverage, real_cov_values=coverage * torch.exp(log_norm))
+            if qs is not None:
+                ret["levels"], ret["level_masses"] = _hip.hpd_levels(lp, qs, log_norm, logw)
+            bad = (~torch.isfinite(log_norm)).nonzero().reshape(-1).tolist()
+        if bad:
+            raise ValueError("hpd_on_grid: the grid's total mass is not finite for the conditional inputs (rows) %s: log p on the grid holds a NaN or "
+                             "an infinity, or no cell carries mass" % bad)
+        return ret
 
     def marginal_log_prob(self, sub_manifold, targets, conditional_input=None, samplesize=100, force_embedding_coordinates=False,
                           force_intrinsic_coordinates=False, max_iterative_batchsize=20, max_tile_elements=2**26, predefined_base=None,
