@@ -10,6 +10,7 @@ Reference line numbers cited below refer to jammy_flows/main/default.py.
 """
 import contextlib
 import copy
+import functools
 import os
 
 import numpy
@@ -204,6 +205,46 @@ def _manifold_chain(layers, direction, x, log_det, extra, sphere_chart_first, x_
         params = extra
     return _hip.mchain(fam, direction, x, log_det, params, _mchain_structs(fam, layers, sphere_chart_first), layers[0].dimension, x_out=x_out,
                        base_logp_in=base_logp_in, want_base_logp=want_base_logp, status=status, pre_ld=pre_ld, pre_blp=pre_blp)
+
+
+def _some(parts):
+    """the entries of a list of per-block sums that exist (None: that block started from nothing and added nothing)"""
+    return [t for t in parts if t is not None]
+
+
+def _last_layer_only(loop, kind, layers, extra):
+    """only_last (:1018) in block loop `loop` -> (the block's last layer, the tail of the parameter row `extra` that belongs to it).  Gradient
+    mode and sampling raise for the sub-pdf kinds they do not take it for; the no-grad log-prob loop ("inv") does not check."""
+    allowed = {"grad": "esi", "fwd": "es", "inv": None}[loop]
+    if allowed is not None and kind not in allowed:
+        raise Exception("Flow type ", kind, " does not supported *only_last*!")
+    return layers[-1:], None if extra is None else _tail_params(extra, layers[-1])
+
+
+_NO_FOLD = dict.fromkeys(("split", "chain", "mchain"), (False, None, None))      # (pdf._fold_plan, for every block but the last)
+
+
+def _unfused_groups(direction, layers, kind, only_last, cur, log_det, extra, status):
+    """a block that is several launches -> (coordinates, log_det) behind its last one: the launch groups of `layers` one after the other,
+    tail-first with tail-first parameter slices for "inv" (:1002-1012), head-first for "fwd"; a run of g layers through gfl.run_chain, any
+    other layer through its own mapping"""
+    inv = direction == "inv"
+    if log_det is None:
+        log_det = torch.zeros(cur.shape[0], dtype=cur.dtype, device=cur.device)
+    groups = _layer_groups(layers)
+    c = extra.shape[1] if (inv and extra is not None) else 0
+    for grp in (reversed(groups) if inv else groups):
+        n = sum(l.total_param_num for l in grp)
+        lo = c - n if inv else c
+        this = None if extra is None else extra[:, lo:lo + n]
+        c = lo if inv else lo + n
+        if type(grp[0]) is gfl.gf_block and not only_last:
+            cur, log_det = gfl.run_chain(grp, direction, cur, log_det, this if this is not None else gfl.chain_permanent_row(grp, cur),
+                                         status=status)[:2]
+        else:
+            kw = {"fix_euclidean_to_sphere_first": True} if (only_last and kind == "s") else {}
+            cur, log_det = (grp[0].inv_flow_mapping if inv else grp[0].flow_mapping)([cur, log_det], extra_inputs=this, **kw)[:2]
+    return cur, log_det
 
 
 def _von_mises_fisher_draws(mu, kappa, n):
@@ -910,11 +951,14 @@ class pdf(nn.Module):
         self._packed_cache[(si, kind)] = (key, packed)
         return packed
 
-    def _block_params(self, si, data_summary, embeds, amort, counter):
-        """extra_inputs row block of sub-pdf si, or None for permanent parameters (:936-993, 1420-1475)."""
+    def _block_params(self, si, data_summary, embeds, amort, counter, inp=None, permanent=None):
+        """extra_inputs row block of sub-pdf si, or None for permanent parameters (:936-993, 1420-1475).  `inp`: the MLP's input where the
+        caller has assembled it.  `permanent` (gradient mode): layers -> their permanent parameters as a row with a graph, returned in place
+        of None; a block without parameters then still gets its (empty) slice of the amortisation block."""
         mlp = self._mlp(si)
         if mlp is not None:
-            inp = self._mlp_input(si, data_summary, embeds)
+            if inp is None:
+                inp = self._mlp_input(si, data_summary, embeds)
             if not isinstance(mlp, HipLinearStack):
                 inp = _hip.as_matrix(inp)
             if amort is not None:
@@ -929,10 +973,10 @@ class pdf(nn.Module):
         if self.amortize_everything:
             assert amort is not None
             n = sum(l.get_total_param_num() for l in self.layer_list[si])
-            if n > 0:
+            if n > 0 or permanent is not None:
                 out = amort[:, counter:counter + n]
                 return out, counter + n
-        return None, counter
+        return (None if permanent is None else permanent(list(self.layer_list[si]))), counter
 
     def _poisson_column(self, si):
         """does the amortisation MLP of sub-pdf si carry log-lambda as an extra last output column?"""
@@ -1007,50 +1051,130 @@ class pdf(nn.Module):
             print(nonconv, " items did not converge in Newton iterations")
 
     # =========================================================================================== log-prob direction
+    def _default_coordinates(self, x, log_det, force_embedding_coordinates, force_intrinsic_coordinates, per_block=None):
+        """the targets of a log-prob call in the pdf's default coordinates -> (x, log_det): from embedding or intrinsic coordinates where one is
+        forced (`per_block` then receives the accumulated log_det after each block's transformation), whose width the targets must have"""
+        if force_embedding_coordinates:
+            assert x.shape[1] == self.total_target_dim_embedded, (x.shape[1], self.total_target_dim_embedded)
+            return self.transform_target_space(x, log_det, transform_from="embedding", transform_to="default", per_block=per_block)
+        if force_intrinsic_coordinates:
+            assert x.shape[1] == self.total_target_dim_intrinsic
+            return self.transform_target_space(x, log_det, transform_from="intrinsic", transform_to="default", per_block=per_block)
+        return x, log_det
+
+    def _step_schedule(self, x, data_summary, only_last, amort, want_base_logp, per_block, lazy):
+        """how this log-prob step issues its blocks -> (independent, lanes, overlap, merge, fold_last).  The blocks of the log-prob direction are independent given the targets
+        (every MLP input is a function of x and the conditional input alone, :946-962): each block returns its OWN log-det / base log-prob
+        and one launch adds them up at the end (_hip.combine_rows), instead of threading the running sums through the blocks as the reference
+        does (:1020-1031) -- unless the caller wants the running sums (`per_block`) or the MLP inputs are assembled block by block (`lazy`)."""
+        rec, B = _hip._RECORDING, x.shape[0]
+        independent = per_block is None and not lazy and len(self.layer_list) > 1
+        # a recorded plan can issue the independent blocks of a SMALL batch on side streams (csrc/plan.hip lanes: their launch / drain tails
+        # overlap), or on one stream without barriers between them
+        lanes = rec is not None and independent and self.plan_lanes > 1 and B <= self.plan_lane_max_rows
+        overlap = rec is not None and independent and not lanes and self.plan_overlap_blocks and B <= self.plan_overlap_max_rows
+        # small batches: the launches of the first two blocks are captured by the library and issued as ONE grid (merged_kernels.hip)
+        merge = independent and not lanes and not overlap and self._merge_candidate(x, data_summary, only_last, amort)
+        # the last block may add the earlier blocks' sums in its epilogue (list order, itself last: the bits of combine_rows) and write
+        # log_prob = log_prob_base + log_det itself (:1110-1117): one launch fewer per step
+        fold_last = independent and want_base_logp and not lanes and not overlap and self.fold_combine
+        return independent, lanes, overlap, merge, fold_last
+
+    def _fold_plan(self, independent, fold_last, want_base_logp, per_block, ld_parts, blp_parts, forced_coordinates):
+        """may the launch of the pdf's LAST block write log_prob itself (its result then carries it as res[3])? -> {launch: (fold, pre_ld,
+        pre_blp)} with the earlier blocks' sums it adds in its epilogue, or None, None where the sums are threaded through the blocks.  Each
+        of the three launches that can fold has its own condition:"""
+        no = _NO_FOLD["split"]
+        # a plain g chain: only where the sums are threaded (a pdf that is, or ends with, one chain), in default coordinates
+        chain = (want_base_logp and not independent and per_block is None and self.fold_combine and not forced_coordinates, None, None)
+        if not fold_last:
+            return {"split": no, "chain": chain, "mchain": no}
+        pre_ld, pre_blp = _some(ld_parts), _some(blp_parts)
+        # the register-resident fused g block: whenever the schedule folds; a manifold chain: unless bins are logged or the sums are too many
+        fits = _hip.BINS_LOG is None and len(pre_ld) <= _hip.COND_GF_MAX_PRE and len(pre_blp) <= _hip.COND_GF_MAX_PRE
+        return {"split": (True, pre_ld, pre_blp), "chain": chain, "mchain": (True, pre_ld, pre_blp) if fits else no}
+
+    def _run_block_inv(self, call, folds, si, block, tgt, out_view, log_det, base_logp):
+        """log-prob direction of sub-pdf si (layers `block`): targets `tgt` -> base coordinates in `out_view`, on top of the incoming sums ->
+        (res, fold) with res = (out_view, log_det, base_logp[, log_prob]); fold: this launch added the step's sums up itself, res[3] = log_prob.
+        `call`: what the blocks of one call share (`counter`, a one-element list: the read position in the amortisation block)"""
+        data_summary, embeds, amort, only_last, want_base_logp, status, counter = call
+        layers, kind = list(block), self.pdf_defs_list[si][0]
+        D = layers[0].dimension
+        sums = {"x_out": out_view, "base_logp_in": base_logp, "want_base_logp": want_base_logp, "status": status}
+        route, w = self._fused_route(si, layers, kind, only_last, amort, tgt)
+        res, fold = None, False
+        if route == "g":
+            # amortisation MLP + g layers in one launch: the per-sample parameter block never reaches HBM
+            larr = _hip.gf_layer_array([l.c_struct() for l in layers])
+            packed = None
+            if self.fused_matrix_arithmetic != "f32" and w[0].shape[0] <= 128:
+                packed = self._packed_w2(si, w[2], w[3], larr, len(layers), D)
+            mlp_in = self._mlp_input(si, data_summary, embeds)
+            if packed is not None:
+                fold, pre_ld, pre_blp = folds["split"]
+                for fold in ((True, False) if fold else (False,)):             # (a launch that declines to fold returns None: then the plain one)
+                    how = dict(sums, base_logp_in=None, want_base_logp=True, pre_ld=pre_ld, pre_blp=pre_blp) if fold else sums
+                    res = _hip.cond_gf_chain_inv_split(mlp_in, w[0], w[1], packed[1], tgt, None if fold else log_det, larr, len(layers), D,
+                                                       kind=packed[0], **how)
+                    if res is not None:
+                        break
+            else:
+                res = _hip.cond_gf_chain_inv(_hip.as_matrix(mlp_in), *w, tgt, log_det, larr, len(layers), D, **sums)
+        elif route == "lowrank":
+            # low-rank AmortizableMLP + g layers in one launch: the parameter block is regenerated per lane from the row's rank-space vector
+            res = _hip.amlp_gf_chain_inv(_hip.as_matrix(self._mlp_input(si, data_summary, embeds)), *w, tgt, log_det,
+                                         _hip.gf_layer_array([l.c_struct() for l in layers]), len(layers), D, **sums)
+        elif route == "m":
+            # w = (family, weights): default amortisation MLP + the manifold chain in one launch, the parameter rows stay in LDS (None: declined)
+            res = _hip.cond_mchain_inv(w[0], _hip.as_matrix(self._mlp_input(si, data_summary, embeds)), *w[1], tgt, log_det,
+                                       _mchain_structs(w[0], layers), D, **sums)
+        if res is not None:
+            return res, fold
+        extra, counter[0] = self._block_params(si, data_summary, embeds, amort, counter[0])
+        if only_last:
+            layers, extra = _last_layer_only("inv", kind, layers, extra)
+        if kind == "e" and gfl.chain_supported(layers):
+            # a pdf that is (or, threading the sums, ends with) one plain g chain: the chain launch writes log_prob = base + log_det itself
+            fold = folds["chain"][0]
+            return gfl.run_chain(layers, "inv", tgt, log_det, gfl.chain_permanent_row(layers, tgt) if extra is None else extra, want_total=fold,
+                                 **sums), fold
+        if _manifold_family(layers) is not None:
+            # the last block adds the earlier blocks' sums itself and writes log_prob (as the fused g block does): no combine launch
+            fold, pre_ld, pre_blp = folds["mchain"]
+            return _manifold_chain(layers, "inv", tgt, log_det, extra, only_last and kind == "s", out_view, base_logp, want_base_logp,
+                                   status, pre_ld=pre_ld, pre_blp=pre_blp), fold
+        cur, log_det = _unfused_groups("inv", layers, kind, only_last, tgt, log_det, extra, status)
+        out_view.copy_(cur)
+        if want_base_logp:
+            base_logp = _hip.normal_logp(out_view, base_logp)
+        return (out_view, log_det, base_logp), False
+
     def _inverse_impl(self, x, log_det, data_summary, amortization_parameters, force_embedding_coordinates, force_intrinsic_coordinates,
                       only_last, want_base_logp, status, per_block=None, last_block=None):
         """`per_block` (optional list): receives the accumulated log_det after the coordinate transformation of each block (first
         len(layer_list) entries, only when a transformation is forced) and after each block's flow -- what the marginal entropies need.
-        `last_block` (with per_block): the flows of the blocks behind it are not evaluated (their base columns stay unwritten)."""
+        `last_block` (with per_block): the flows of the blocks behind it are not evaluated (their base columns stay unwritten).
+        The loop: the step's schedule, then per block (its lane or order in a recorded plan, its launches, its sums), then the sums combined."""
         _hip.require_device(x, log_det)
-        if force_embedding_coordinates:
-            assert x.shape[1] == self.total_target_dim_embedded, (x.shape[1], self.total_target_dim_embedded)
-            x, log_det = self.transform_target_space(x, log_det, transform_from="embedding", transform_to="default", per_block=per_block)
-        elif force_intrinsic_coordinates:
-            assert x.shape[1] == self.total_target_dim_intrinsic
-            x, log_det = self.transform_target_space(x, log_det, transform_from="intrinsic", transform_to="default", per_block=per_block)
-        else:
-            assert x.shape[1] == self.total_target_dim, (x.shape[1], self.total_target_dim)
+        x, log_det = self._default_coordinates(x, log_det, force_embedding_coordinates, force_intrinsic_coordinates, per_block)
+        assert x.shape[1] == self.total_target_dim, (x.shape[1], self.total_target_dim)
         if amortization_parameters is not None:
             assert amortization_parameters.shape[1] == self.total_number_amortizable_params
-        B = x.shape[0]
-        base = torch.empty((B, self.total_base_dim), dtype=x.dtype, device=x.device)
-        base_logp = None
+        assert last_block is None or per_block is not None
+        base, base_logp = torch.empty((x.shape[0], self.total_base_dim), dtype=x.dtype, device=x.device), None
         embeds = self._conditioning_rows(x, data_summary)
         lazy = embeds is None
-        if lazy:
-            embeds = []
-        counter = 0
-        # The blocks of the log-prob direction are independent given the targets (every MLP input is a function of x and the conditional
-        # input alone, :946-962): each block returns its OWN log-det / base log-prob and one launch adds them up at the end
-        # (_hip.combine_rows), instead of threading the running sums through the blocks as the reference does (:1020-1031).  A recorded plan
-        # can then issue the blocks of a SMALL batch on side streams (csrc/plan.hip lanes): their launch / drain tails overlap.
-        assert last_block is None or per_block is not None
-        independent = per_block is None and not lazy and len(self.layer_list) > 1
-        ld_parts = [] if log_det is None else [log_det]
-        blp_parts = []
-        rec = _hip._RECORDING
-        lanes = rec is not None and independent and self.plan_lanes > 1 and B <= self.plan_lane_max_rows
-        overlap = rec is not None and independent and not lanes and self.plan_overlap_blocks and B <= self.plan_overlap_max_rows
-        # small batches: the launches of the first two blocks are captured by the library and issued as ONE grid (merged_kernels.hip)
-        merge = (independent and not lanes and not overlap and self._merge_candidate(x, data_summary, only_last, amortization_parameters))
+        n_blocks = len(self.layer_list)
+        independent, lanes, overlap, merge, fold_last = self._step_schedule(x, data_summary, only_last, amortization_parameters, want_base_logp,
+                                                                            per_block, lazy)
+        ld_parts, blp_parts = ([] if log_det is None else [log_det]), []
+        embeds = [] if lazy else embeds
+        call = (data_summary, embeds, amortization_parameters, only_last, want_base_logp, status, [0])
+        rec = _hip._RECORDING if (lanes or overlap) else None        # (the plan being recorded)
         if lanes:
             rec.fork()
-        n_blocks = len(self.layer_list)
-        # the last block may add the earlier blocks' sums in its epilogue (list order, itself last: the bits of combine_rows) and write
-        # log_prob = log_prob_base + log_det itself (:1110-1117): one launch fewer per step
-        fold_last = independent and want_base_logp and not lanes and not overlap and self.fold_combine
-        folded_total = None
+        total = None
         if merge:
             _hip.merge_begin()
         try:
@@ -1065,94 +1189,21 @@ class pdf(nn.Module):
                         if want_base_logp:
                             blp_parts.append(base_logp)
                     log_det, base_logp = None, None
-                    if lanes:                             # the last block stays on the caller's stream
+                    if lanes:                       # the last block stays on the caller's stream
                         rec.set_lane(0 if si == n_blocks - 1 else 1 + si % (self.plan_lanes - 1))
-                    if overlap and si == 1:               # the blocks after the first may run beside their predecessors (no barrier bit)
+                    if overlap and si == 1:         # the blocks after the first may run beside their predecessors (no barrier bit)
                         rec.set_any_order(True)
                 a, b = self.target_dim_indices[si]
-                tgt = x[:, a:b]
                 ba, bb = self.base_dim_indices[si]
-                out_view = base[:, ba:bb]
-                layers = list(block)
-                kind = self.pdf_defs_list[si][0]
-                D = layers[0].dimension
-                fold_here = fold_last and si == n_blocks - 1
-                route, w = self._fused_route(si, layers, kind, only_last, amortization_parameters, x)
-                res, fold = None, False                   # fold: this launch added the step's sums up itself, res[3] = log_prob
-                if route == "g":
-                    # amortisation MLP + g layers in one launch: the per-sample parameter block never reaches HBM
-                    larr = _hip.gf_layer_array([l.c_struct() for l in layers])
-                    packed = None
-                    if self.fused_matrix_arithmetic != "f32" and w[0].shape[0] <= 128:
-                        packed = self._packed_w2(si, w[2], w[3], larr, len(layers), D)
-                    if packed is not None:
-                        mlp_in = self._mlp_input(si, data_summary, embeds)
-                        if fold_here:
-                            res = _hip.cond_gf_chain_inv_split(mlp_in, w[0], w[1], packed[1], tgt, None, larr, len(layers), D, x_out=out_view,
-                                                               want_base_logp=True, status=status, kind=packed[0],
-                                                               pre_ld=[t for t in ld_parts if t is not None], pre_blp=[t for t in blp_parts if t is not None])
-                            fold = res is not None
-                        if res is None:
-                            res = _hip.cond_gf_chain_inv_split(mlp_in, w[0], w[1], packed[1], tgt, log_det, larr, len(layers), D, x_out=out_view,
-                                                               base_logp_in=base_logp, want_base_logp=want_base_logp, status=status, kind=packed[0])
-                    else:
-                        res = _hip.cond_gf_chain_inv(_hip.as_matrix(self._mlp_input(si, data_summary, embeds)), *w, tgt, log_det, larr, len(layers), D,
-                                                     x_out=out_view, base_logp_in=base_logp, want_base_logp=want_base_logp, status=status)
-                elif route == "lowrank":
-                    # low-rank AmortizableMLP + g layers in one launch: the parameter block is regenerated per lane from the row's rank-space vector
-                    res = _hip.amlp_gf_chain_inv(_hip.as_matrix(self._mlp_input(si, data_summary, embeds)), *w, tgt, log_det,
-                                                 _hip.gf_layer_array([l.c_struct() for l in layers]), len(layers), D,
-                                                 x_out=out_view, base_logp_in=base_logp, want_base_logp=want_base_logp, status=status)
-                elif route == "m":
-                    # default amortisation MLP + the manifold chain in one launch: the parameter rows stay in LDS (None: declined)
-                    fam, ws = w
-                    res = _hip.cond_mchain_inv(fam, _hip.as_matrix(self._mlp_input(si, data_summary, embeds)), *ws, tgt, log_det,
-                                               _mchain_structs(fam, layers), D, x_out=out_view, base_logp_in=base_logp, want_base_logp=want_base_logp,
-                                               status=status)
-                if res is None:
-                    extra, counter = self._block_params(si, data_summary, embeds, amortization_parameters, counter)
-                    if only_last:
-                        layers = layers[-1:]
-                        extra = None if extra is None else _tail_params(extra, layers[0])
-                    if kind == "e" and gfl.chain_supported(layers):
-                        # a pdf that is (or, threading the sums, ends with) one plain g chain: the chain launch writes log_prob = base + log_det itself
-                        fold = (want_base_logp and not independent and si == n_blocks - 1 and per_block is None and self.fold_combine
-                                and not force_embedding_coordinates and not force_intrinsic_coordinates)
-                        res = gfl.run_chain(layers, "inv", tgt, log_det, gfl.chain_permanent_row(layers, x) if extra is None else extra, x_out=out_view,
-                                            base_logp_in=base_logp, want_base_logp=want_base_logp, status=status, want_total=fold)
-                    elif _manifold_family(layers) is not None:
-                        pl = pb_ = None
-                        if fold_here and _hip.BINS_LOG is None:
-                            # the last block adds the earlier blocks' sums itself and writes log_prob (as the fused g block does): no combine launch
-                            pl, pb_ = [t for t in ld_parts if t is not None], [t for t in blp_parts if t is not None]
-                            if len(pl) > _hip.COND_GF_MAX_PRE or len(pb_) > _hip.COND_GF_MAX_PRE:
-                                pl = pb_ = None
-                        fold = pl is not None
-                        res = _manifold_chain(layers, "inv", tgt, log_det, extra, only_last and kind == "s", out_view, base_logp, want_base_logp, status,
-                                              pre_ld=pl, pre_blp=pb_)
-                    else:
-                        if log_det is None:
-                            log_det = torch.zeros(B, dtype=x.dtype, device=x.device)
-                        cur, end = tgt, 0 if extra is None else extra.shape[1]
-                        for grp in reversed(_layer_groups(layers)):       # tail-first parameter slices (:1002-1012)
-                            n = sum(l.total_param_num for l in grp)
-                            this = None if extra is None else extra[:, end - n:end]
-                            if type(grp[0]) is gfl.gf_block and not only_last:
-                                cur, log_det = gfl.run_chain(grp, "inv", cur, log_det, this if this is not None else gfl.chain_permanent_row(grp, x),
-                                                             status=status)[:2]
-                            else:
-                                kw = {"fix_euclidean_to_sphere_first": True} if (only_last and kind == "s") else {}
-                                cur, log_det = grp[0].inv_flow_mapping([cur, log_det], extra_inputs=this, **kw)[:2]
-                            end -= n
-                        out_view.copy_(cur)
-                        if want_base_logp:
-                            base_logp = _hip.normal_logp(out_view, base_logp)
-                        res = (out_view, log_det, base_logp)
+                tgt = x[:, a:b]
+                folds = _NO_FOLD if si < n_blocks - 1 else self._fold_plan(independent, fold_last, want_base_logp, per_block, ld_parts, blp_parts,
+                                                                           force_embedding_coordinates or force_intrinsic_coordinates)
+                res, fold = self._run_block_inv(call, folds, si, block, tgt, base[:, ba:bb], log_det, base_logp)
                 log_det = res[1]
                 if want_base_logp:
                     base_logp = res[2]
                 if fold:
-                    folded_total = res[3]
+                    total = res[3]                        # (log_det / base_logp are the totals already)
                 if lazy:
                     embeds.append(block[-1]._embedding_conditional_return(tgt))
                 if per_block is not None:
@@ -1163,10 +1214,7 @@ class pdf(nn.Module):
             if merge:
                 _hip.merge_abort()
             raise
-        total = None
-        if folded_total is not None:
-            total = folded_total                          # log_det / base_logp are the totals already
-        elif independent:
+        if total is None and independent:
             ld_parts.append(log_det)
             if want_base_logp:
                 blp_parts.append(base_logp)
@@ -1175,9 +1223,8 @@ class pdf(nn.Module):
                 rec.join()
             if overlap:
                 rec.set_any_order(False)                  # the combine launch is ordered: it waits for every block
-            log_det, base_logp, total = _hip.combine_rows([t for t in ld_parts if t is not None], [t for t in blp_parts if t is not None],
-                                                          want_total=want_base_logp)
-        elif want_base_logp:
+            log_det, base_logp, total = _hip.combine_rows(_some(ld_parts), _some(blp_parts), want_total=want_base_logp)
+        elif total is None and want_base_logp:
             total = _hip.add_rows(base_logp, log_det)     # (:1110-1117)
         return base, log_det, base_logp, total
 
@@ -1290,6 +1337,27 @@ class pdf(nn.Module):
             return torch.zeros((1, 0), dtype=like.dtype, device=like.device)
         return torch.cat(parts).reshape(1, -1)
 
+    def _block_cot(self, v, si, layers, tgt, inp):
+        """v -> J_block^-T v of the pure g block si at targets `tgt` (MLP input `inp`, both detached), or None where the launch declines: one
+        launch for a block that runs as one; a wide block cut into several (_layer_groups: a CU's LDS) carries the co-vector and the
+        coordinates from launch to launch, last group first, parameters sliced tail-first like the block's"""
+        with torch.no_grad():
+            if inp is not None:
+                params = self._mlp(si)(inp)
+                params = params[:, :-1] if self._poisson_column(si) else params
+            else:
+                params = gfl.chain_permanent_row(layers, tgt)
+            cur, c1 = tgt, params.shape[1]
+            for grp in reversed(_layer_groups(layers)):
+                n = sum(l.total_param_num for l in grp)
+                res = _hip.gf_chain_inv_cot(cur, params[:, c1 - n:c1], _hip.gf_layer_array([l.c_struct() for l in grp]), len(grp),
+                                            grp[0].dimension, v, want_x_out=True)
+                if res is None:
+                    return None
+                v, cur = res
+                c1 -= n
+            return v
+
     def _forward_with_grad(self, x, conditional_input, amortization_parameters, force_embedding_coordinates, force_intrinsic_coordinates,
                            only_last, collect=None):
         """forward() with a torch.autograd graph: d log_prob / d (x, conditional_input, MLP weights, permanent layer parameters).
@@ -1299,54 +1367,31 @@ class pdf(nn.Module):
         pure g chains `cot`: v -> J_block^-T v, the co-vector carried through the block's layers by one launch per launch group
         (jf_gf_chain_inv_cot; a wide block such as e33 "gg" is several groups, it used to fall back to the dense D x D solve) -- what
         the implicit-function adjoint of sampling needs (_differentiable_sample)."""
-        log_det0 = None
-        if force_embedding_coordinates:          # the chart changes ahead of the block loop, with a graph (autograd.SphereEmbeddingFn)
-            assert x.shape[1] == self.total_target_dim_embedded, (x.shape[1], self.total_target_dim_embedded)
-            x, log_det0 = self.transform_target_space(x, None, transform_from="embedding", transform_to="default")
-        elif force_intrinsic_coordinates:
-            assert x.shape[1] == self.total_target_dim_intrinsic
-            x, log_det0 = self.transform_target_space(x, None, transform_from="intrinsic", transform_to="default")
+        # the chart changes ahead of the block loop, with a graph (autograd.SphereEmbeddingFn)
+        x, log_det = self._default_coordinates(x, None, force_embedding_coordinates, force_intrinsic_coordinates)
         amort = amortization_parameters
         if amort is not None:
             assert amort.shape[1] == self.total_number_amortizable_params
         counter = 0
+        permanent = functools.partial(self._permanent_row_with_grad, like=x)
 
-        def block_params(si, kind, layers, inp, mlp):
-            """(layers to run, their parameter block with grad): the MLP output (own or per-sample weights), a slice of the amortisation block,
-            or the permanent parameters (:936-993); only_last (:1018): the block's last layer alone, with the tail of the row"""
+        def block_params(si, kind, layers, inp):
+            """(layers to run, their parameter block with grad); only_last (:1018): the block's last layer alone, with the tail of the row"""
             nonlocal counter
-            if mlp is not None:
-                if amort is not None:
-                    n = mlp.num_amortization_params
-                    out = mlp(inp, extra_inputs=amort[:, counter:counter + n])
-                    counter += n
-                else:
-                    out = mlp(inp)
-                out = out[:, :-1] if self._poisson_column(si) else out
-            elif self.amortize_everything:
-                n = sum(l.get_total_param_num() for l in layers)
-                out = amort[:, counter:counter + n]
-                counter += n
-            else:
-                out = self._permanent_row_with_grad(layers, x)
-            if not only_last:
-                return layers, out
-            if kind not in ("e", "s", "i"):
-                raise Exception("Flow type ", kind, " does not supported *only_last*!")
-            return layers[-1:], _tail_params(out, layers[-1])
+            out, counter = self._block_params(si, conditional_input, embeds, amort, counter, inp=inp, permanent=permanent)
+            return _last_layer_only("grad", kind, layers, out) if only_last else (layers, out)
         _hip.require_device(x)
         self._poll_status()
         _hip.release_keepalive()                 # (tensors of the previous step that crossed streams: the streams have met since, _hip.KEEPALIVE)
         status = _hip.new_status(x.device) if self.check_status else None
         B = x.shape[0]
-        log_det = log_det0
         base_logp = None
         bases = []
         embeds = []
         # independent blocks on side streams (self.train_streams): each block starts from zero sums, the sums are added after the loop
         n_blocks = len(self.layer_list)
         side = None
-        if self.train_streams > 1 and n_blocks > 1 and collect is None and log_det0 is None:
+        if self.train_streams > 1 and n_blocks > 1 and collect is None and log_det is None:
             side = self._train_stream_objs.get(x.device)
             if side is None or len(side) != self.train_streams - 1:
                 side = self._train_stream_objs[x.device] = [torch.cuda.Stream(device=x.device) for _ in range(self.train_streams - 1)]
@@ -1360,15 +1405,7 @@ class pdf(nn.Module):
             layers = list(block)
             kind = self.pdf_defs_list[si][0]
             mlp = self._mlp(si)
-            inp = None
-            if mlp is not None:
-                pieces = []
-                if conditional_input is not None:
-                    pieces.append(conditional_input[si] if type(conditional_input) == list else conditional_input)
-                pieces += embeds
-                if not pieces:
-                    raise Exception("extra conditional input is empty but required for encoding!")
-                inp = torch.cat(pieces, dim=1) if len(pieces) > 1 else pieces[0]
+            inp = self._mlp_input(si, conditional_input, embeds) if mlp is not None else None
             st = None
             if side is not None:
                 log_det, base_logp = None, None
@@ -1398,14 +1435,14 @@ class pdf(nn.Module):
                         larr = _hip.gf_layer_array([l.c_struct() for l in layers])
                         out, log_det, base_logp = autograd.LowRankGfChainFn.apply(t2, u2, b2, tgt, log_det, base_logp, larr, len(layers), D, status)
                     else:
-                        used, params = block_params(si, kind, layers, inp, mlp)
+                        used, params = block_params(si, kind, layers, inp)
                         larr = _hip.gf_layer_array([l.c_struct() for l in used])
                         out, log_det, base_logp = autograd.GfChainInvFn.apply(tgt, log_det, params, base_logp, larr, len(used), D, status)
                 else:
                     # a block of several launches, last group first, parameters sliced tail-first (:1002-1012): a Euclidean block mixing 'g' runs
                     # with other layers ('t'), or a manifold block (mixed families, e.g. "mo": one launch per layer)
                     from ..layers.euclidean.multivariate_normal import mvn_block
-                    used, params = block_params(si, kind, layers, inp, mlp)
+                    used, params = block_params(si, kind, layers, inp)
                     if kind == "e":
                         groups = _layer_groups(used)
                     else:
@@ -1453,45 +1490,22 @@ class pdf(nn.Module):
                 cot = None
                 if (kind == "e" and all(type(l) is gfl.gf_block for l in layers) and layers[0].dimension <= _hip.GF_MAX_DIM and not only_last
                         and amort is None):
-                    def cot(v, si=si, layers=layers, tgt=tgt.detach(), inp=None if inp is None else inp.detach(), mlp=mlp):
-                        with torch.no_grad():
-                            if mlp is not None:
-                                params = mlp(inp)
-                                params = params[:, :-1] if self._poisson_column(si) else params
-                            else:
-                                params = gfl.chain_permanent_row(layers, tgt)
-                            # one launch for a block that runs as one; a wide block cut into several (_layer_groups: a CU's LDS) carries the
-                            # co-vector and the coordinates from launch to launch, last group first, parameters sliced tail-first like the block's
-                            cur, c1 = tgt, params.shape[1]
-                            for grp in reversed(_layer_groups(layers)):
-                                n = sum(l.total_param_num for l in grp)
-                                res = _hip.gf_chain_inv_cot(cur, params[:, c1 - n:c1], _hip.gf_layer_array([l.c_struct() for l in grp]), len(grp),
-                                                            grp[0].dimension, v, want_x_out=True)
-                                if res is None:
-                                    return None
-                                v, cur = res
-                                c1 -= n
-                            return v
+                    cot = functools.partial(self._block_cot, si=si, layers=layers, tgt=tgt.detach(), inp=None if inp is None else inp.detach())
                 collect.append({"a": a, "b": b, "y": out, "cot": cot, "coupled": mlp is not None and len(embeds) > 0})
             emb = block[-1]._embedding_conditional_return(tgt.detach()) if not tgt.requires_grad else autograd.embed(tgt, kind, layers[-1])
             embeds.append(emb)
+        total = None
         if side is not None:
             for st in side:
                 main_stream.wait_stream(st)               # every block's outputs are complete before the caller's stream adds them up
             if autograd.COMBINE_ROWS_FN and all(t is not None and t.dim() == 1 for t in ld_parts + blp_parts):
                 # the blocks' sums and the total in one launch (autograd.CombineRowsFn)
                 total, base_logp = autograd.CombineRowsFn.apply(len(ld_parts), *ld_parts, *blp_parts)
-                base = torch.cat(bases, dim=1) if len(bases) > 1 else bases[0]
-                self._defer_status(status)
-                return total, base_logp, base
-            log_det = ld_parts[0]
-            for t in ld_parts[1:]:
-                log_det = log_det + t
-            base_logp = blp_parts[0]
-            for t in blp_parts[1:]:
-                base_logp = base_logp + t
+            else:
+                log_det, base_logp = sum(ld_parts[1:], ld_parts[0]), sum(blp_parts[1:], blp_parts[0])
         base = torch.cat(bases, dim=1) if len(bases) > 1 else bases[0]
-        total = base_logp + log_det
+        if total is None:
+            total = base_logp + log_det
         self._defer_status(status)
         return total, base_logp, base
 
@@ -1500,6 +1514,42 @@ class pdf(nn.Module):
         return self.forward(x, conditional_input=conditional_input, **kwargs)[0]
 
     # =========================================================================================== sampling direction
+    def _run_block_fwd(self, call, si, block, cur, out_view, log_det):
+        """sampling direction of sub-pdf si (layers `block`): base coordinates `cur` -> targets in `out_view` -> res = (out_view, log_det)"""
+        data_summary, embeds, amort, only_last, status, counter = call
+        layers, kind = list(block), self.pdf_defs_list[si][0]
+        D = layers[0].dimension
+        route, w = self._fused_route(si, layers, kind, only_last, amort, cur)
+        res = None
+        if route == "g" and self.fused_matrix_arithmetic != "f32" and w[0].shape[0] <= 128:
+            # amortisation MLP + the g layers' solves in one launch, parameters regulated once in the MFMA result registers
+            larr = _hip.gf_layer_array([l.c_struct() for l in layers])
+            packed = self._packed_w2(si, w[2], w[3], larr, len(layers), D)
+            if packed is not None:
+                res = _hip.cond_gf_chain_fwd_split(self._mlp_input(si, data_summary, embeds), w[0], w[1], packed[1], cur, log_det, larr,
+                                                   len(layers), D, x_out=out_view, status=status, kind=packed[0])
+        elif route == "lowrank":
+            # low-rank AmortizableMLP + the g layers' solves in one launch (float64, ranks <= 8): no (B, N) parameter block in HBM
+            res = _hip.amlp_gf_chain_fwd(_hip.as_matrix(self._mlp_input(si, data_summary, embeds)), *w, cur, log_det,
+                                         _hip.gf_layer_array([l.c_struct() for l in layers]), len(layers), D, x_out=out_view, status=status)
+        elif route == "m":
+            # w = (family, weights): default amortisation MLP + the manifold chain forwards in one launch, the parameter rows stay in LDS
+            res = _hip.cond_mchain_fwd(w[0], _hip.as_matrix(self._mlp_input(si, data_summary, embeds)), *w[1], cur, log_det,
+                                       _mchain_structs(w[0], layers), D, x_out=out_view, status=status)
+        if res is not None:                               # (the fused launches above return None where they decline)
+            return res
+        extra, counter[0] = self._block_params(si, data_summary, embeds, amort, counter[0])
+        if only_last:
+            layers, extra = _last_layer_only("fwd", kind, layers, extra)
+        if kind == "e" and gfl.chain_supported(layers):
+            return gfl.run_chain(layers, "fwd", cur, log_det, gfl.chain_permanent_row(layers, cur) if extra is None else extra, x_out=out_view,
+                                 status=status)
+        if _manifold_family(layers) is not None:
+            return _manifold_chain(layers, "fwd", cur, log_det, extra, only_last and kind == "s", out_view, None, False, status)
+        cur, log_det = _unfused_groups("fwd", layers, kind, only_last, cur, log_det, extra, status)
+        out_view.copy_(cur)
+        return out_view, log_det
+
     def all_layer_forward(self, x, log_det, data_summary, amortization_parameters=None, force_embedding_coordinates=False,
                           force_intrinsic_coordinates=False, only_last=False, status=None, per_block=None):
         """autoregressive forward mapping base -> target -> (x, log_det)  (:1373-1531).  `per_block` (optional list) receives the accumulated
@@ -1509,80 +1559,27 @@ class pdf(nn.Module):
             assert amortization_parameters.shape[1] == self.total_number_amortizable_params
         else:
             assert not self.amortize_everything
-        B = x.shape[0]
-        out = torch.empty((B, self.total_target_dim), dtype=x.dtype, device=x.device)
+        out = torch.empty((x.shape[0], self.total_target_dim), dtype=x.dtype, device=x.device)
         # the MLP input rows cat[conditional_input, embed(x_0), ...] (:1440-1456) as SEGMENTS of the output buffer, which the blocks fill one
         # after the other: block si reads the columns of the blocks before it where they are (the consumers of _mlp_input with segment
         # support), as in the log-prob direction -- no torch.cat, no embedding launch per sphere block
         embeds = self._conditioning_rows(out, data_summary)
         lazy = embeds is None
-        if lazy:
-            embeds = []
-        counter = 0
+        embeds = [] if lazy else embeds
+        call = (data_summary, embeds, amortization_parameters, only_last, status, [0])
         for si, block in enumerate(self.layer_list):
-            kind = self.pdf_defs_list[si][0]
-            layers = list(block)
-            D = layers[0].dimension
             ba, bb = self.base_dim_indices[si]
             a, b = self.target_dim_indices[si]
-            cur, out_view = x[:, ba:bb], out[:, a:b]
-            route, w = self._fused_route(si, layers, kind, only_last, amortization_parameters, x)
-            res = None
-            if route == "g" and self.fused_matrix_arithmetic != "f32" and w[0].shape[0] <= 128:
-                # amortisation MLP + the g layers' solves in one launch, parameters regulated once in the MFMA result registers
-                larr = _hip.gf_layer_array([l.c_struct() for l in layers])
-                packed = self._packed_w2(si, w[2], w[3], larr, len(layers), D)
-                if packed is not None:
-                    res = _hip.cond_gf_chain_fwd_split(self._mlp_input(si, data_summary, embeds), w[0], w[1], packed[1], cur, log_det, larr,
-                                                       len(layers), D, x_out=out_view, status=status, kind=packed[0])
-            elif route == "lowrank":
-                # low-rank AmortizableMLP + the g layers' solves in one launch (float64, ranks <= 8): no (B, N) parameter block in HBM
-                res = _hip.amlp_gf_chain_fwd(_hip.as_matrix(self._mlp_input(si, data_summary, embeds)), *w, cur, log_det,
-                                             _hip.gf_layer_array([l.c_struct() for l in layers]), len(layers), D, x_out=out_view, status=status)
-            elif route == "m":
-                # default amortisation MLP + the manifold chain forwards in one launch: the parameter rows stay in LDS
-                fam, ws = w
-                res = _hip.cond_mchain_fwd(fam, _hip.as_matrix(self._mlp_input(si, data_summary, embeds)), *ws, cur, log_det,
-                                           _mchain_structs(fam, layers), D, x_out=out_view, status=status)
-            if res is None:                               # (the fused launches above return None where they decline)
-                extra, counter = self._block_params(si, data_summary, embeds, amortization_parameters, counter)
-                if only_last:
-                    if kind not in "es":
-                        raise Exception("Flow type ", kind, " does not supported *only_last*!")
-                    layers = layers[-1:]
-                    extra = None if extra is None else _tail_params(extra, layers[0])
-                if kind == "e" and gfl.chain_supported(layers):
-                    res = gfl.run_chain(layers, "fwd", cur, log_det, gfl.chain_permanent_row(layers, x) if extra is None else extra, x_out=out_view,
-                                        status=status)
-                elif _manifold_family(layers) is not None:
-                    res = _manifold_chain(layers, "fwd", cur, log_det, extra, only_last and kind == "s", out_view, None, False, status)
-                else:
-                    if log_det is None:
-                        log_det = torch.zeros(B, dtype=x.dtype, device=x.device)
-                    c = 0
-                    for grp in _layer_groups(layers):     # head-first parameter slices
-                        n = sum(l.total_param_num for l in grp)
-                        this = None if extra is None else extra[:, c:c + n]
-                        c += n
-                        if type(grp[0]) is gfl.gf_block and not only_last:
-                            cur, log_det = gfl.run_chain(grp, "fwd", cur, log_det, this if this is not None else gfl.chain_permanent_row(grp, x),
-                                                         status=status)
-                        else:
-                            kw = {"fix_euclidean_to_sphere_first": True} if (only_last and kind == "s") else {}
-                            cur, log_det = grp[0].flow_mapping([cur, log_det], extra_inputs=this, **kw)[:2]
-                    out_view.copy_(cur)
-                    res = (out_view, log_det)
-            log_det = res[1]
+            out_view = out[:, a:b]
+            log_det = self._run_block_fwd(call, si, block, x[:, ba:bb], out_view, log_det)[1]
             if lazy:
                 embeds.append(block[-1]._embedding_conditional_return(out_view))
             if per_block is not None:
                 per_block.append(log_det)
-        x_new = out
-        if force_embedding_coordinates:
-            x_new, log_det = self.transform_target_space(x_new, log_det, transform_from="default", transform_to="embedding", per_block=per_block)
-        elif force_intrinsic_coordinates:
-            x_new, log_det = self.transform_target_space(x_new, log_det, transform_from="default", transform_to="intrinsic", per_block=per_block)
-        return x_new, log_det
+        if force_embedding_coordinates or force_intrinsic_coordinates:
+            return self.transform_target_space(out, log_det, transform_from="default", per_block=per_block,
+                                               transform_to="embedding" if force_embedding_coordinates else "intrinsic")
+        return out, log_det
 
     def _obtain_sample(self, conditional_input=None, predefined_target_input=None, samplesize=1, seed=None, amortization_parameters=None,
                        force_embedding_coordinates=False, force_intrinsic_coordinates=False, failsafe_crosscheck_tolerance=None, dtype=None,
