@@ -1935,9 +1935,10 @@ def t_layer(direction, x, log_det, params, struct, D, x_out=None, base_logp_in=N
     return _flow_result(x_out, ld_out, blp_out, want_base_logp)
 
 
-def _chain_inv_bwd(name, x, params, D, layers, g_xout, g_ld, g_blp, status):
+def _chain_inv_bwd(name, x, params, D, layers, g_xout, g_ld, g_blp, status, unsupported_ok=False):
     """the launch t_layer_inv_bwd and mchain_inv_bwd share: `layers` is the argument between the row count and the upstream gradients
-    -> (g_x (B, D), g_params (B, P), (1, P) zeroed for the launch's atomics when one row is shared, or None without parameters)"""
+    -> (g_x (B, D), g_params (B, P), (1, P) zeroed for the launch's atomics when one row is shared, or None without parameters); with
+    unsupported_ok, None when the library declines the launch (JF_ERR_UNSUPPORTED)"""
     dev = require_device(x, params, g_xout, g_ld, g_blp, status)
     x = _rowmajor(x)
     B = x.shape[0]
@@ -1948,10 +1949,10 @@ def _chain_inv_bwd(name, x, params, D, layers, g_xout, g_ld, g_blp, status):
         g_p = torch.zeros((1, P), dtype=x.dtype, device=x.device) if pb == 1 else torch.empty((B, P), dtype=x.dtype, device=x.device)
     held, g_args = _cotangents(g_xout, g_ld, g_blp)
     g_x = torch.empty((B, D), dtype=x.dtype, device=x.device)
-    _launch(name + _suffix(x), "bcast" if pb == 1 else "per-sample",
-            (_ptr(x), x.stride(0), pptr, pstride, pb, B) + layers + g_args
-            + (_ptr(g_x), g_x.stride(0), _ptr(g_p), g_p.stride(0) if g_p is not None else 0, _ptr(status)), dev)
-    return g_x, g_p
+    ok = _launch(name + _suffix(x), "bcast" if pb == 1 else "per-sample",
+                 (_ptr(x), x.stride(0), pptr, pstride, pb, B) + layers + g_args
+                 + (_ptr(g_x), g_x.stride(0), _ptr(g_p), g_p.stride(0) if g_p is not None else 0, _ptr(status)), dev, unsupported_ok=unsupported_ok)
+    return (g_x, g_p) if ok else None
 
 
 def t_layer_inv_bwd(x, params, struct, D, g_xout, g_ld, g_blp, status=None):
@@ -1961,10 +1962,32 @@ def t_layer_inv_bwd(x, params, struct, D, g_xout, g_ld, g_blp, status=None):
     return g_x, g_p
 
 
-def mchain_inv_bwd(fam, x, params, layer_structs, dim, g_xout, g_ld, g_blp, status=None):
-    """vector-Jacobian product of mchain(fam, 'inv', ...): -> (g_x (B, dim), g_params in the shape of `params`)."""
-    g_x, g_p = _chain_inv_bwd("jf_%s_chain_inv_bwd" % fam, x, params, dim, (len(layer_structs), mchain_layer_array(fam, layer_structs)),
-                              g_xout, g_ld, g_blp, status)
+_MCHAIN_BWD_DECLINED = set()
+
+
+def mchain_inv_bwd(fam, x, params, layer_structs, dim, g_xout, g_ld, g_blp, status=None, widths=None):
+    """vector-Jacobian product of mchain(fam, 'inv', ...): -> (g_x (B, dim), g_params in the shape of `params`).
+    widths (the layers' parameter row lengths): a chain whose adjoint the library declines as one launch -- the smallest row tile with the
+    whole chain's parameter rows is beyond a CU's LDS -- is cut in two, each half tried again: the input of the half applied last (layers
+    0 .. h-1) comes from one forward launch over the other half, its x gradient is the x_out cotangent of that half."""
+    n = len(layer_structs)
+    cut = widths is not None and n > 1
+    # the decline depends on the descriptors, the dtype and the parameter regime alone: found by trial once, remembered
+    key = (fam, tuple(bytes(s) for s in layer_structs), x.dtype, params is not None and params.shape[0] == 1) if cut else None
+    res = None
+    if key is None or key not in _MCHAIN_BWD_DECLINED:
+        res = _chain_inv_bwd("jf_%s_chain_inv_bwd" % fam, x, params, dim, (n, mchain_layer_array(fam, layer_structs)), g_xout, g_ld, g_blp, status,
+                             unsupported_ok=cut)
+    if res is None:
+        _MCHAIN_BWD_DECLINED.add(key)
+        h = n // 2
+        lo = sum(widths[:h])
+        head, tail = params[:, :lo], params[:, lo:]
+        x_mid = mchain(fam, "inv", x, None, tail, layer_structs[h:], dim)[0]
+        g_mid, g_head = mchain_inv_bwd(fam, x_mid, head, layer_structs[:h], dim, g_xout, g_ld, g_blp, status, widths[:h])
+        g_x, g_tail = mchain_inv_bwd(fam, x, tail, layer_structs[h:], dim, g_mid, g_ld, None, status, widths[h:])
+        return g_x, torch.cat([g_head, g_tail], dim=1)
+    g_x, g_p = res
     if g_p is None:
         g_p = torch.zeros((params.shape[0] if params is not None else 1, 0), dtype=g_x.dtype, device=g_x.device)
     return g_x, g_p

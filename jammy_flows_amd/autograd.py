@@ -484,10 +484,10 @@ class MChainInvFn(torch.autograd.Function):
     Backward: jf_*_chain_inv_jvp launches (forward-mode passes through the very same device code instantiated on dual numbers)."""
 
     @staticmethod
-    def forward(ctx, x, log_det, params, base_logp_in, fam, structs, dim, status):
+    def forward(ctx, x, log_det, params, base_logp_in, fam, structs, dim, status, widths=None):
         res = _hip.mchain(fam, "inv", x.detach(), None if log_det is None else log_det.detach(), params.detach(), structs, dim,
                           base_logp_in=None if base_logp_in is None else base_logp_in.detach(), want_base_logp=True, status=status)
-        ctx.meta = (fam, structs, dim)
+        ctx.meta = (fam, structs, dim, widths)       # widths (the layers' row lengths): lets the adjoint cut a chain the library declines as one launch
         ctx.set_materialize_grads(False)             # unused outputs arrive as None (the kernels take NULL), not as zero-filled tensors
         ctx.has = (log_det is not None, base_logp_in is not None)
         ctx.save_for_backward(x, params)
@@ -497,9 +497,9 @@ class MChainInvFn(torch.autograd.Function):
     @_side_stream_safe
     def backward(ctx, g_xout, g_ld, g_blp):
         x, params = ctx.saved_tensors
-        fam, structs, dim = ctx.meta
-        g_x, g_params = _hip.mchain_inv_bwd(fam, x, params, structs, dim, g_xout, g_ld, g_blp)
-        return (g_x, g_ld if ctx.has[0] else None, g_params, g_blp if ctx.has[1] else None, None, None, None, None)
+        fam, structs, dim, widths = ctx.meta
+        g_x, g_params = _hip.mchain_inv_bwd(fam, x, params, structs, dim, g_xout, g_ld, g_blp, widths=widths)
+        return (g_x, g_ld if ctx.has[0] else None, g_params, g_blp if ctx.has[1] else None, None, None, None, None, None)
 
 
 class TLayerInvFn(torch.autograd.Function):

@@ -953,7 +953,8 @@ template <typename T> static int64_t gb_lds_query(int32_t D, int32_t n_layers, c
         a.D = D; a.n_layers = n_layers;
         const int64_t dual = (int64_t)((size_t)JF_MAX_D_GF * GX_THREADS * sizeof(Dual<T>) + 16 * sizeof(T) + (size_t)GX_THREADS * a.spline_tab * sizeof(Dual<T>));
         const int64_t rev = gfx_chain_rev_lds_bytes<T>(a, bcast != 0);
-        return rev > dual ? rev : dual;                            // (either kernel may take the launch: JF_G_BWD_DUAL)
+        static const int dual_replay = getenv("JF_G_BWD_DUAL") ? atoi(getenv("JF_G_BWD_DUAL")) : 0;
+        return dual_replay > 0 ? dual : rev;                       // (the kernel that takes the launch: the reverse sweep unless JF_G_BWD_DUAL=1)
     }
     const int G = gb_group_width(D);
     for (int l = 0; l < n_layers; ++l) if (layers[l].hh_iter > (G > GB_MAX_HH ? G : GB_MAX_HH)) return JF_ERR_UNSUPPORTED;

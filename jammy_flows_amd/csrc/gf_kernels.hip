@@ -247,7 +247,8 @@ template <typename T, bool FWD> __global__ void __launch_bounds__(GX_THREADS) gf
     const int tid = threadIdx.x, D = a.D;
     const XCol<T> x{lds + tid}, z{lds + JF_MAX_D_GF * GX_THREADS + tid};
     T* tab = lds + 2 * JF_MAX_D_GF * GX_THREADS + tid * a.spline_tab;
-    const int64_t row = (int64_t)blockIdx.x * GX_THREADS + tid;
+    const int64_t row = (int64_t)blockIdx.x * blockDim.x + tid;      // (blockDim.x = a.group <= GX_THREADS: fewer lanes, and knot tables, per workgroup
+                                                                     //  where GX_THREADS tables are beyond the LDS; the columns keep their stride)
     const bool row_valid = row < a.B;
     const int64_t rrow = row_valid ? row : a.B - 1;
     for (int d = 0; d < D; ++d) x[d] = a.x[rrow * a.xs + d];
@@ -391,8 +392,28 @@ template <typename T> static int fill_args(GfChainArgs<T>& a, const T* params, i
         a.tab_offset = (int)elems;
         elems += (size_t)64 * a.spline_tab;
     }
+    // per-sample rows of a spline chain with many bins: the 64 / G parameter rows and the 64 lane-private knot tables of a workgroup are beyond
+    // a CU (64 bins in float64: 100 KB of tables, 102 KB of rows at D = 2).  The kernel of a wider group runs the same rows with fewer of them
+    // per workgroup (lanes g >= D idle, as they do wherever D is not a power of two) down to one row per workgroup.
+    a.group = G;
+    if (!bcast && any_spline && !ext) {
+        while (elems * sizeof(T) > (size_t)LDS_LIMIT && a.group < 64) {
+            a.group *= 2;
+            for (int l = 0; l < n_layers; ++l) a.L[l].vec_ok = 0;      // (the grouped staging is sized for group_width(D))
+            elems = (size_t)(64 / a.group) * a.tile_stride;
+            a.tab_offset = (int)elems;
+            elems += (size_t)64 * a.spline_tab;
+        }
+    }
     lds_bytes = elems * sizeof(T);
-    if (ext) lds_bytes = ((size_t)2 * JF_MAX_D_GF * GX_THREADS + (any_spline ? (size_t)GX_THREADS * a.spline_tab : 0)) * sizeof(T);
+    if (ext) {                                           // one lane per row: a.group = lanes per workgroup, halved while their knot tables do not fit
+        a.group = GX_THREADS;
+        for (;;) {
+            lds_bytes = ((size_t)2 * JF_MAX_D_GF * GX_THREADS + (any_spline ? (size_t)a.group * a.spline_tab : 0)) * sizeof(T);
+            if (lds_bytes <= (size_t)LDS_LIMIT || !any_spline || a.group <= 16) break;
+            a.group >>= 1;
+        }
+    }
     a.tiles_per_block = 1;                               // broadcast: set by launch_g from the kernel's occupancy
     if (lds_bytes > (size_t)LDS_LIMIT) return JF_ERR_UNSUPPORTED;
     return JF_OK;
@@ -494,10 +515,10 @@ template <typename T, bool FWD> static int launch(const GfChainArgs<T>& a, int D
     if (ext) {
         auto k = gfx_chain_kernel<T, FWD>;
         if (lds_bytes > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        jf::launch(k, dim3((unsigned)((a.B + GX_THREADS - 1) / GX_THREADS)), dim3(GX_THREADS), lds_bytes, st, a, bcast ? (int64_t)0 : a.ps);
+        jf::launch(k, dim3((unsigned)((a.B + a.group - 1) / a.group)), dim3(a.group), lds_bytes, st, a, bcast ? (int64_t)0 : a.ps);
         return check_launch();
     }
-    switch (group_width(D)) {
+    switch (a.group) {
         case 1: return launch_g<T, 1, FWD>(a, bcast, lds_bytes, st);
         case 2: return launch_g<T, 2, FWD>(a, bcast, lds_bytes, st);
         case 4: return launch_g<T, 4, FWD>(a, bcast, lds_bytes, st);

@@ -227,15 +227,24 @@ __global__ void __launch_bounds__(GX_THREADS) gfx_chain_rev_kernel(const GfBwdAr
     T* xw0 = xin0 + (size_t)a.n_layers * D * GX_THREADS;                            // [D][GX_THREADS] working column (values)
     T* gc0 = xw0 + (size_t)D * GX_THREADS;                                          // [D][GX_THREADS] gradient column
     T* gn0 = gc0 + (size_t)D * GX_THREADS;                                          // [D][GX_THREADS] gradient column (next)
-    T* tab0 = gn0 + (size_t)D * GX_THREADS;                                         // [GX_THREADS][spline_tab]
-    T* accp = tab0 + (size_t)GX_THREADS * a.spline_tab;                            // [P] (permanent parameters)
+    // a.lanes < 64 (many spline bins: GX_THREADS knot tables are beyond the LDS): the first `lw` lanes of a wave own a row and a table, lane
+    // i >= lw repeats lane i % lw -- same row, same parameters, so it writes the same words into the same table in the same instruction -- and
+    // is inactive: it emits zeros and stores nothing.  The waves do not share tables.  This rests on owner and repeating lanes running every
+    // table build and every table read in the same instruction of one wave: NO table write or read may ever sit under a branch that depends on
+    // `active` / `owner` (today only sink.active differs between them, and GradSink::emit touches no table).
+    const int lw = a.lanes > 0 ? a.lanes : 64;
+    const int slot = (tid >> 6) * lw + (tid & (lw - 1));                            // row within the tile and table
+    const int tile_rows = (GX_THREADS / 64) * lw;
+    const bool owner = (tid & 63) < lw;
+    T* tab0 = gn0 + (size_t)D * GX_THREADS;                                         // [tile_rows][spline_tab]
+    T* accp = tab0 + (size_t)tile_rows * a.spline_tab;                             // [P] (permanent parameters)
     const bool bcast = pstep == 0;
     size_t off_d = (size_t)((accp + (bcast ? a.n_params_total : 0)) - reinterpret_cast<T*>(smem_raw)) * sizeof(T);
     off_d = (off_d + 15) & ~(size_t)15;
     Du* xd0 = reinterpret_cast<Du*>(smem_raw + off_d);                              // [D][GX_THREADS] the rotation's dual column
     const XCol<T> xw{xw0 + tid}, gc{gc0 + tid}, gn{gn0 + tid};
     const XCol<Du> xd{xd0 + tid};
-    T* tab = tab0 + tid * a.spline_tab;
+    T* tab = tab0 + slot * a.spline_tab;
     if (bcast) {
         for (int j = tid; j < a.n_params_total; j += GX_THREADS) accp[j] = T(0);
         __syncthreads();
@@ -244,11 +253,12 @@ __global__ void __launch_bounds__(GX_THREADS) gfx_chain_rev_kernel(const GfBwdAr
     bool first_tile = true;
     for (int64_t tile = blockIdx.x; tile < tiles_total || (bcast && first_tile); tile += gridDim.x) {
         first_tile = false;
-        const int64_t row = tile * GX_THREADS + tid;
-        const bool active = row < a.B && tile < tiles_total;
-        const int64_t rrow = active ? row : a.B - 1;
-        const T gld = (a.g_ld && active) ? a.g_ld[rrow] : T(0);
-        const T gblp = (a.g_blp && active) ? a.g_blp[rrow] : T(0);
+        const int64_t row = tile * tile_rows + slot;
+        const bool in_range = row < a.B && tile < tiles_total;
+        const bool active = owner && in_range;                     // (a repeating lane computes exactly what its owner does and keeps nothing)
+        const int64_t rrow = in_range ? row : a.B - 1;
+        const T gld = (a.g_ld && in_range) ? a.g_ld[rrow] : T(0);
+        const T gblp = (a.g_blp && in_range) ? a.g_blp[rrow] : T(0);
         const T* prow = a.params + rrow * pstep;
         GradSink<T> sink;
         sink.row = (!bcast && active) ? a.g_params + row * a.gps : nullptr;
@@ -273,7 +283,7 @@ __global__ void __launch_bounds__(GX_THREADS) gfx_chain_rev_kernel(const GfBwdAr
                 }
             }
         }
-        for (int d = 0; d < D; ++d) gc[d] = (a.g_xout && active) ? a.g_xout[rrow * a.gxos + d] : T(0);
+        for (int d = 0; d < D; ++d) gc[d] = (a.g_xout && in_range) ? a.g_xout[rrow * a.gxos + d] : T(0);
         // ---- reverse sweep
         for (int l = 0; l < a.n_layers; ++l) {
             const GfLayerDev<T>& o = a.L[l];
@@ -339,14 +349,33 @@ __global__ void __launch_bounds__(GX_THREADS) gfx_chain_rev_kernel(const GfBwdAr
     status_add(a.status, JF_STATUS_NONFINITE, bad_any);
 }
 
+template <typename T> int64_t gfx_chain_rev_lds_bytes(const GfBwdArgs<T>& a, bool bcast);
+// row-owning lanes per wave: 64, halved while the knot tables do not fit a CU's LDS (down to 4)
+template <typename T> static int gfx_chain_rev_lanes(GfBwdArgs<T> a, bool bcast) {
+    a.lanes = 64;
+    while ((size_t)gfx_chain_rev_lds_bytes<T>(a, bcast) > 160 * 1024 && a.spline_tab > 0 && a.lanes > 4) a.lanes >>= 1;
+    return a.lanes;
+}
+// LDS bytes of the launch with a.lanes row-owning lanes per wave; a.lanes == 0: with the lane count gfx_chain_rev_launch would choose
 template <typename T> int64_t gfx_chain_rev_lds_bytes(const GfBwdArgs<T>& a, bool bcast) {
-    const size_t plain = 16 + ((size_t)(a.n_layers + 3) * a.D * GX_THREADS + (size_t)GX_THREADS * a.spline_tab + (bcast ? (size_t)a.n_params_total : 0)) * sizeof(T);
+    if (a.lanes == 0) {
+        GfBwdArgs<T> b = a;
+        b.lanes = gfx_chain_rev_lanes<T>(b, bcast);
+        return gfx_chain_rev_lds_bytes<T>(b, bcast);
+    }
+    const size_t tile_rows = (size_t)(GX_THREADS / 64) * a.lanes;
+    const size_t plain = 16 + ((size_t)(a.n_layers + 3) * a.D * GX_THREADS + tile_rows * a.spline_tab + (bcast ? (size_t)a.n_params_total : 0)) * sizeof(T);
     return (int64_t)(((plain + 15) & ~(size_t)15) + (size_t)a.D * GX_THREADS * sizeof(DualN<T, GXR_N>));
 }
 
 template <typename T> int gfx_chain_rev_launch(GfBwdArgs<T> a, bool bcast, int64_t ps, int64_t blocks, int64_t tiles, void* stream) {
+    a.lanes = gfx_chain_rev_lanes<T>(a, bcast);                                   // fewer rows, and knot tables, per workgroup (see the kernel)
     const size_t lds = (size_t)gfx_chain_rev_lds_bytes<T>(a, bcast);
     if (lds > 160 * 1024) return JF_ERR_UNSUPPORTED;
+    if (a.lanes < 64) {
+        tiles = (a.B + (GX_THREADS / 64) * a.lanes - 1) / ((GX_THREADS / 64) * a.lanes);
+        if (!bcast) blocks = tiles;
+    }
     auto k = gfx_chain_rev_kernel<T>;
     if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     jf::launch(k, dim3((unsigned)blocks), dim3(GX_THREADS), lds, (hipStream_t)stream, a, bcast ? (int64_t)0 : ps, tiles);

@@ -79,6 +79,7 @@ template <typename T> struct GfBwdArgs {
     int pk0[JF_MAX_CHAIN];                    // broadcast regime: first packed component record of every layer (gf_chain_bwd_kernel)
     int slsh;                                 // broadcast regime: log2 of the accumulator slots per parameter (see gf_chain_bwd_kernel)
     int spline_tab;                           // general-option kernel: words of a lane's knot table (0: no spline stretch in the chain)
+    int lanes;                                // reverse-sweep kernel: lanes per wave with a row of their own (0 = all 64; fewer where the knot tables take it)
 };
 
 // general-option chains (jf_gf_ext.h), reverse mode (gf_rev_kernels.hip): launch and the LDS bytes it takes

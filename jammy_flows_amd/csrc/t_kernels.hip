@@ -7,6 +7,8 @@
 // The reference multiplies by an explicit inverse built from sub-determinants (matrix_fns.py:88-141); here the triangular system is solved by
 // forward substitution in registers (same result; D <= 32, kernels instantiated for 8 / 16 / 32 coordinates).  One sample per lane; row: [offset D if model_offset][log-diagonal 1 | D][lower D(D-1)/2].
 //   jf_t_layer_inv_* / jf_t_layer_fwd_* / jf_t_layer_inv_bwd_* (backward: one forward + one backward substitution, see t_bwd_kernel)
+#include <cstdlib>
+
 #include "jf_dual.h"
 #include "jf_gf.h"
 
@@ -120,33 +122,41 @@ template <typename T, bool FWD, int MD> __global__ void __launch_bounds__(256) t
 // Per-sample parameters: g_params (B, P) rows.  Broadcast parameters: the workgroup's sums over ALL its row tiles in LDS, added to g_params
 // once at the end -- a resident set of workgroups walks the tiles (manifold_bwd_kernels.hip: one atomic per 64-row tile and parameter was
 // most of such a kernel's time).
-template <typename T, int MD> __global__ void __launch_bounds__(64) t_bwd_kernel(const TArgs<T> a) {
+// STAGED = false (per-sample parameters only): the [P][64] tile is beyond the LDS (float64 full covariance from D = 24 on: 324 rows of 512 B), every
+// lane reads its own parameter row from global memory instead, as the forward kernel does -- the same values through the same arithmetic, so the
+// result equals the staged kernel's bit for bit.  Two instantiations, not one pointer that is LDS or global: the tile stays an LDS pointer.
+template <typename T, int MD, bool STAGED> __global__ void __launch_bounds__(64) t_bwd_kernel(const TArgs<T> a) {
     using Du = Dual<T>;
     extern __shared__ __align__(16) unsigned char smem_raw[];
+    const bool bcast = STAGED && a.bcast;
     T* tile = reinterpret_cast<T*>(smem_raw);                         // [P][64] (per-sample) or [P] (broadcast): lane-contiguous columns
-    T* accp = tile + (a.P > 0 ? a.P : 1) * (a.bcast ? 1 : 64);         // broadcast: [P] gradient sums
+    T* accp = tile + (a.P > 0 ? a.P : 1) * (bcast ? 1 : 64);           // broadcast: [P] gradient sums
     const int tid = threadIdx.x;
     const int D = a.o.D, cov = a.o.cov;
-    if (a.bcast) {
-        for (int j = tid; j < a.P; j += 64) { tile[j] = a.params[j]; accp[j] = T(0); }
-    } else {
-        const int64_t row = (int64_t)blockIdx.x * 64 + tid;
-        const int64_t rrow = row < a.B ? row : a.B - 1;
-        for (int j = 0; j < a.P; ++j) tile[j * 64 + tid] = a.params[rrow * a.ps + j];
+    const int64_t own_row = (int64_t)blockIdx.x * 64 + tid;          // per-sample parameters: the one tile of this workgroup
+    const int64_t own_rrow = own_row < a.B ? own_row : a.B - 1;
+    if constexpr (STAGED) {
+        if (bcast) {
+            for (int j = tid; j < a.P; j += 64) { tile[j] = a.params[j]; accp[j] = T(0); }
+        } else {
+            for (int j = 0; j < a.P; ++j) tile[j * 64 + tid] = a.params[own_rrow * a.ps + j];
+        }
+        __syncthreads();
     }
-    __syncthreads();
     TDev<Du> od;                                                      // the width regulator on single duals: d log(diagonal) / d raw
     od.cov = cov; od.model_offset = a.o.model_offset; od.D = D;
     od.w.width_mode = a.o.w.width_mode; od.w.clamp_widths = a.o.w.clamp_widths;
     od.w.wmin = Du(a.o.w.wmin); od.w.inv_wmax = Du(a.o.w.inv_wmax); od.w.lw_lo = Du(a.o.w.lw_lo); od.w.lw_hi = Du(a.o.w.lw_hi);
-    const T* p = a.bcast ? tile : tile + tid;
-    const int64_t pstep = a.bcast ? 1 : 64;
+    const T* p;
+    int64_t pstep;
+    if constexpr (STAGED) { p = bcast ? tile : tile + tid; pstep = bcast ? 1 : 64; }
+    else { p = a.params + own_rrow * a.ps; pstep = 1; }
     auto P = [&](int i) -> T { return p[i * pstep]; };
     const int c0 = a.o.model_offset ? D : 0;                          // first diagonal parameter
     const int n_diag = cov == JF_T_IDENTITY ? 0 : cov == JF_T_DIAGONAL_SYMMETRIC ? 1 : D;
     const int lo = c0 + D;                                            // first strictly-lower entry (full covariance)
     const int64_t n_tiles = (a.B + 63) / 64;
-    const int64_t t_end = a.bcast ? n_tiles : (int64_t)blockIdx.x + 1;    // per-sample parameters: the tile staged above
+    const int64_t t_end = bcast ? n_tiles : (int64_t)blockIdx.x + 1;      // per-sample parameters: the workgroup's own tile
     for (int64_t tile_i = blockIdx.x; tile_i < t_end; tile_i += gridDim.x) {
         const int64_t row = tile_i * 64 + tid;
         const bool active = row < a.B;
@@ -154,7 +164,7 @@ template <typename T, int MD> __global__ void __launch_bounds__(64) t_bwd_kernel
         // a parameter's gradient of this row: stored (per-sample) or summed over the wave into the workgroup's accumulators (broadcast)
         auto emit = [&](int j, T v) {
             if (!active) v = T(0);
-            if (a.bcast) {
+            if (bcast) {
 #pragma unroll
                 for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
                 if (tid == 0) accp[j] += v;
@@ -209,7 +219,7 @@ template <typename T, int MD> __global__ void __launch_bounds__(64) t_bwd_kernel
             if (a.o.model_offset) emit(d, -zb[d]);
         }
     }
-    if (a.bcast) {
+    if (bcast) {
         __syncthreads();
         for (int j = tid; j < a.P; j += 64) atomicAdd(a.g_params + j, accp[j]);
     }
@@ -259,9 +269,14 @@ static int t_layer_bwd(const T* x, int64_t xs, const T* params, int64_t ps, int3
     if (B == 0) return JF_OK;
     a.x = x; a.xs = xs; a.params = params; a.ps = ps; a.bcast = pb == 1; a.B = B;
     a.g_xout = g_xout; a.gxos = gxos; a.g_ld = g_ld; a.g_blp = g_blp; a.g_x = g_x; a.gxs = gxs; a.g_params = g_params; a.gps = gps; a.status = status;
-    const size_t lds = ((size_t)(a.P > 0 ? a.P : 1) * (a.bcast ? 1 : 64) + (a.bcast ? (size_t)a.P : 0)) * sizeof(T);
-    if (lds > 160 * 1024) return JF_ERR_UNSUPPORTED;
-    auto k = D <= 8 ? t_bwd_kernel<T, 8> : D <= 16 ? t_bwd_kernel<T, 16> : t_bwd_kernel<T, 32>;
+    size_t lds = ((size_t)(a.P > 0 ? a.P : 1) * (a.bcast ? 1 : 64) + (a.bcast ? (size_t)a.P : 0)) * sizeof(T);
+    // per-sample parameters: the tile is staged where it fits the LDS, else the lanes read their rows from global memory (same result, bit for bit).
+    // JF_T_BWD_STAGE=0 (read at every call) takes the second kernel at every size: the check of that equality.
+    bool staged = a.bcast || lds <= 160 * 1024;
+    if (!a.bcast) { const char* e = getenv("JF_T_BWD_STAGE"); if (e && atoi(e) == 0) staged = false; }
+    if (!staged) lds = 0;
+    auto k = staged ? (D <= 8 ? t_bwd_kernel<T, 8, true> : D <= 16 ? t_bwd_kernel<T, 16, true> : t_bwd_kernel<T, 32, true>)
+                    : (D <= 8 ? t_bwd_kernel<T, 8, false> : D <= 16 ? t_bwd_kernel<T, 16, false> : t_bwd_kernel<T, 32, false>);
     if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     int64_t grid = (B + 63) / 64;
     if (a.bcast) {                                                 // a resident set of workgroups walks the tiles (eight per CU: the kernel is light)

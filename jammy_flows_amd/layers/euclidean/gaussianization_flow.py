@@ -123,6 +123,23 @@ class gf_block(euclidean_base.euclidean_base):
 
         self._row_cache = None
         self._c_struct = None
+        if nonlinear_stretch_type != "classic":
+            self._refuse_unless_one_layer_fits()
+
+    def _refuse_unless_one_layer_fits(self):
+        """rq_splines: the knot tables and parameter rows of ONE layer must fit a CU's LDS in float64, forward and (where the stretch has a
+        backward kernel) backward, broadcast and per sample (the library's own bookkeeping, no GPU needed) -- else no launch exists for this layer and its first use would fail: refused here,
+        like more than JF_SPLINE_MAX_BINS bins"""
+        try:
+            arr = _hip.gf_layer_array([self.c_struct()])
+            # (the backward of the spline stretch exists up to 8 dimensions: beyond, a layer evaluates and samples only, whatever its bin count)
+            fits = all(_hip.gf_chain_fits(arr, 1, self.dimension, torch.float64, bcast, backward) for bcast in (True, False)
+                       for backward in ((False, True) if self.dimension <= 8 else (False,)))
+        except _hip.HipUnavailable:
+            return
+        if not fits:
+            raise NotImplementedError("g layer with rq_splines: %d bins at %d dimensions%s do not fit the HIP kernels' on-chip memory (float64)"
+                                      % (self.num_kde, self.dimension, " with general options" if self.has_extended_options else ""))
 
     # ------------------------------------------------------------------------------------------------------
     def c_struct(self):

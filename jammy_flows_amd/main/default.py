@@ -1459,7 +1459,8 @@ class pdf(nn.Module):
                         if fam is not None:
                             # (only_last on a sphere: the last layer also takes the sphere -> plane chart, fix_euclidean_to_sphere_first, :1018-1031)
                             out, log_det, blp = autograd.MChainInvFn.apply(out, log_det, this, blp_in, fam,
-                                                                           _mchain_structs(fam, grp, only_last and kind == "s"), grp[0].dimension, status)
+                                                                           _mchain_structs(fam, grp, only_last and kind == "s"), grp[0].dimension, status,
+                                                                           [l.total_param_num for l in grp])
                         elif type(grp[0]) is gfl.gf_block:
                             larr = _hip.gf_layer_array([l.c_struct() for l in grp])
                             out, log_det, blp = autograd.GfChainInvFn.apply(out, log_det, this, blp_in, larr, len(grp), grp[0].dimension, status)
