@@ -768,7 +768,9 @@ int32_t jf_plan_read_timing(int64_t plan, double* ms_sum_per_op, int32_t n_ops, 
  *   coverage probabilities (ascending, n <= 1024); hist[i] (i <= n, int64, ADDED to) = rows whose first threshold with twice < thr is i
  *   (i = n: none), so #(twice < thr[i]) = hist[0] + ... + hist[i].  twice_out nullable.
  * jf_segment_reduce: the sample means of pdf.entropy (main/default.py:2263-2454): out[g] = -mean_s in[g, s] (mode 0) or
- *   logsumexp_s in[g, s] - log S (mode 1), in row-major (n_seg, seg_len).
+ *   logsumexp_s in[g, s] - log S (mode 1), in row-major (n_seg, seg_len).  Mode 1 takes torch.logsumexp's special values: any NaN in the
+ *   segment gives NaN; otherwise any +inf gives +inf; otherwise a segment of -inf alone gives -inf (-inf entries beside finite ones are zero
+ *   terms).  Mode 0 propagates by plain IEEE arithmetic.  JF_ERR_BADARG: seg_len < 1, a mode other than 0 / 1.
  * ------------------------------------------------------------------------------------------------------------ */
 int jf_coverage_histogram_f32(const float* log_prob_base, int64_t B, double log_at_zero, const float* thresholds, int32_t n, int64_t* hist,
                               float* twice_out, void* stream);
@@ -779,8 +781,10 @@ int jf_segment_reduce_f64(const double* in, int64_t n_seg, int64_t seg_len, int3
 
 /* jf_segment_moments: the per-group sums of pdf.marginal_moments (main/default.py:2590-3030).  x (n_seg * S, w <= 64), row stride xs;
  *   sum_out[g, a] = sum_s x[g, s, a]; cmom_out[g, a, b] = sum_s (x[g, s, a] - mean_a)(x[g, s, b] - mean_b) (centred: sample covariance * (S - 1));
- *   argmax_out[g] (int64) = the first s with the largest logp[g, s] -- logp and argmax_out are nullable together.  Every sum runs in a fixed
- *   order inside the segment's own workgroup: a group's result does not depend on the other groups of the launch. */
+ *   argmax_out[g] (int64) = the first s with the largest logp[g, s] -- logp and argmax_out are nullable together.  Ties pick the first index;
+ *   a NaN never wins (the maximum is taken over the entries that are not NaN, -inf among them); a segment of -inf alone or of NaN alone gives 0.
+ *   Every sum runs in a fixed order inside the segment's own workgroup: a group's result does not depend on the other groups of the launch.
+ *   S = 1 gives sum_out = x and cmom_out = 0 exactly; cmom_out is exactly symmetric. */
 int jf_segment_moments_f32(const float* x, int64_t xs, const float* logp, int64_t n_seg, int64_t S, int32_t w, float* sum_out, float* cmom_out,
                            int64_t* argmax_out, void* stream);
 int jf_segment_moments_f64(const double* x, int64_t xs, const double* logp, int64_t n_seg, int64_t S, int32_t w, double* sum_out, double* cmom_out,
@@ -798,6 +802,8 @@ int jf_segment_moments_f64(const double* x, int64_t xs, const double* logp, int6
  * (g, i), so out[g, i] carries the same bits for every i-range and every number of groups.  One workgroup stages and derives ONE parameter
  * row (g, j) in LDS -- as the broadcast regime of the chain entry points does for its single row -- and walks the group's targets against it.
  * Solver status is reported through `status` (nullable) as the chain entry points do.
+ * The log-sum-exp over j takes torch.logsumexp's special values: any NaN pair value gives NaN; otherwise any +inf gives +inf; otherwise pair
+ * values of -inf alone give -inf (-inf - log S = -inf); `add` is then added by plain IEEE arithmetic.
  * jf_pair_gf: a chain of 'g' layers within the limits of the broadcast regime of jf_gf_chain_inv (D <= 64, Householder rotations, no
  *   center_mean / add_skewness, LDS fit as jf_gf_chain_lds_bytes reports); otherwise JF_ERR_UNSUPPORTED.
  * jf_pair_mchain: a chain of manifold layers of family fam ('r', 'o', 'm', 'f', 'v' as a character code; layers: array of the family's
@@ -826,6 +832,9 @@ int jf_pair_mchain_f64(int32_t fam, const double* x, int64_t xs, const double* p
  * x / params / tile, J < 1, i0 < 0, i1 < i0, i1 > N, xgs neither 0 nor >= i1.  Solver status through `status` (nullable).
  * jf_grid_reduce: out[g * ni + i] = add[g * ni + i] + log( sum_j exp( tile[g, j, i] + logw[g * J + j] ) ), j in the fixed order 0 .. J-1, no
  *   atomics; add is nullable (= 0); logw = NULL: uniform weights 1 / J, computed as m + log(s) - log(J) (the bits of the pairwise reduction).
+ *   Special values follow torch.logsumexp over the terms t_j = tile + logw as they are formed: any NaN term gives NaN (tile = +inf against
+ *   logw = -inf is one); otherwise any +inf term gives +inf; otherwise terms of -inf alone (a group of zero weights) give -inf; add is then
+ *   added by plain IEEE arithmetic.
  *   JF_ERR_BADARG: null tile / out, J < 1, negative n_groups / ni; JF_ERR_UNSUPPORTED: n_groups * J > 2^31 - 1 (no jf_grid_* tile is larger).
  * ------------------------------------------------------------------------------------------------------------ */
 int jf_grid_gf_f32(const float* x, int64_t xs, int64_t xgs, const float* params, int64_t ps, int64_t n_groups, int32_t J, int32_t N, int32_t i0,

@@ -95,6 +95,8 @@ template <typename T> static int coverage_hist(const T* lpb, int64_t B, double l
 }
 
 // ---- entropy reductions: out[g] = -mean_s in[g, s]  (mode 0)   or   log-mean-exp_s in[g, s]  (mode 1: logsumexp - log S)
+// Mode 1 takes torch.logsumexp's special values: an infinite maximum is replaced by 0 in the subtraction (exp(inf - inf) would be NaN), so
+// any NaN gives NaN, else any +inf gives +inf, else all -inf gives -inf; a finite maximum leaves every operation as it was.
 template <typename T>
 __global__ void __launch_bounds__(64) segment_reduce_kernel(const T* __restrict__ in, int64_t n_seg, int64_t seg_len, int mode, T* __restrict__ out) {
     const int64_t g = blockIdx.x;
@@ -110,6 +112,7 @@ __global__ void __launch_bounds__(64) segment_reduce_kernel(const T* __restrict_
         T m = -INFINITY;
         for (int64_t i = lane; i < seg_len; i += 64) m = M<T>::max(m, p[i]);
         for (int off = 32; off > 0; off >>= 1) m = M<T>::max(m, __shfl_xor(m, off, 64));
+        if (!M<T>::finite(m)) m = T(0);                   // (m is never NaN: fmax skips NaN)
         T s = T(0);
         for (int64_t i = lane; i < seg_len; i += 64) s += M<T>::exp(p[i] - m);
         for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
@@ -291,10 +294,15 @@ template <typename T> static int tanh_bwd(const T* g, const T* y, int64_t n, T* 
 // pre-activation z, and its backward g * act'(z).  code: JF_ACT_RELU .. JF_ACT_IDENTITY (include/jammy_hip.h).
 template <typename T> __device__ __forceinline__ T act_value(int code, T z) {
     switch (code) {
-        case JF_ACT_RELU: return z > T(0) ? z : T(0);
+        case JF_ACT_RELU: return z <= T(0) ? T(0) : z;                                          // (NaN stays NaN, as torch.relu)
         case JF_ACT_SOFTPLUS: return z > T(20) ? z : M<T>::log1p(M<T>::exp(z));                 // torch.nn.Softplus(beta=1, threshold=20)
         case JF_ACT_ELU: return z > T(0) ? z : M<T>::expm1(z);                                  // alpha = 1
-        case JF_ACT_SWISH: return z / (T(1) + M<T>::exp(-z));                                   // x sigmoid(beta x), beta = 1 (extra_functions.py:62-68)
+        case JF_ACT_SWISH: {                                                                    // x sigmoid(beta x), beta = 1 (extra_functions.py:62-68)
+            const T e = M<T>::exp(-z);
+            if (e < T(INFINITY) || e != e) return z / (T(1) + e);
+            const T t = M<T>::exp(T(0.5) * z);            // exp(-z) overflowed: z e^z, the product rounded into the denormals once
+            return (z * t) * t;
+        }
         case JF_ACT_SQUARE: return z * z;
         default: return z;
     }
@@ -302,9 +310,18 @@ template <typename T> __device__ __forceinline__ T act_value(int code, T z) {
 template <typename T> __device__ __forceinline__ T act_deriv(int code, T z) {
     switch (code) {
         case JF_ACT_RELU: return z > T(0) ? T(1) : T(0);
-        case JF_ACT_SOFTPLUS: return z > T(20) ? T(1) : T(1) / (T(1) + M<T>::exp(-z));
+        case JF_ACT_SOFTPLUS: {
+            if (z > T(20)) return T(1);
+            const T e = M<T>::exp(-z);
+            return (e < T(INFINITY) || e != e) ? T(1) / (T(1) + e) : M<T>::exp(z);              // exp(-z) overflowed: sigmoid(z) = e^z
+        }
         case JF_ACT_ELU: return z > T(0) ? T(1) : M<T>::exp(z);
-        case JF_ACT_SWISH: { const T sg = T(1) / (T(1) + M<T>::exp(-z)); return sg * (T(1) + z * (T(1) - sg)); }
+        case JF_ACT_SWISH: {
+            const T e = M<T>::exp(-z);
+            if (e < T(INFINITY) || e != e) { const T sg = T(1) / (T(1) + e); return sg * (T(1) + z * (T(1) - sg)); }
+            const T t = M<T>::exp(T(0.5) * z);            // exp(-z) overflowed: (1 + z) e^z
+            return ((T(1) + z) * t) * t;
+        }
         case JF_ACT_SQUARE: return T(2) * z;
         default: return T(1);
     }

@@ -217,7 +217,9 @@ template <typename T, int D> static int launch_pair_gfb(const GfChainArgs<T>& a,
 
 // ---------------------------------------------------------------------------------------------------------- reduction over j
 // out[g * ostride + o0 + i] = add[same] + log sum_j exp(tile[g, j, i] + logw[g * J + j]); WEIGHTED = false: uniform weights 1 / J, computed as
-// m + log(s) - log(J).  j runs 0 .. J-1 in this order for every (g, i).
+// m + log(s) - log(J).  j runs 0 .. J-1 in this order for every (g, i).  torch.logsumexp's special values over the terms tile + logw: an
+// infinite maximum is replaced by 0 in the subtraction, so any NaN term gives NaN, else any +inf gives +inf, else all -inf gives -inf; a finite
+// maximum leaves every operation as it was.
 template <typename T, bool WEIGHTED>
 __global__ void __launch_bounds__(256) pair_reduce_kernel(const T* __restrict__ tile, const T* __restrict__ logw, const T* __restrict__ add,
                                                           int64_t n_groups, int J, int ni, int64_t ostride, int o0, T* __restrict__ out) {
@@ -229,6 +231,7 @@ __global__ void __launch_bounds__(256) pair_reduce_kernel(const T* __restrict__ 
     const T* w = WEIGHTED ? logw + grp * J : nullptr;
     T m = -INFINITY;
     for (int j = 0; j < J; ++j) m = M<T>::max(m, WEIGHTED ? p[(int64_t)j * ni] + w[j] : p[(int64_t)j * ni]);
+    if (!M<T>::finite(m)) m = T(0);                       // (m is never NaN: fmax skips NaN)
     T s = T(0);
     for (int j = 0; j < J; ++j) s += M<T>::exp((WEIGHTED ? p[(int64_t)j * ni] + w[j] : p[(int64_t)j * ni]) - m);
     const int64_t o = grp * ostride + o0 + il;
