@@ -1562,14 +1562,18 @@ def as_matrix(inp):
     return inp.materialize() if isinstance(inp, SegInput) else inp
 
 
-def conditioning_rows(segments, B, dtype, device):
+def conditioning_rows(segments, B, dtype, device, out=None):
     """segments: list of (tensor (B, n), kind) with kind 0 = copy the columns, 1 = S1 angle -> (cos, sin), 2 = S2 (theta, phi) -> (x, y, z).
-    Returns the (B, sum of output widths) row block cat[...] in ONE launch (the amortisation MLPs read prefixes of it)."""
+    Returns the (B, sum of output widths) row block cat[...] in ONE launch (the amortisation MLPs read prefixes of it).
+    out: a caller's (B, width) buffer of `dtype` with unit column stride (any row stride) to write into instead."""
     if not 1 <= len(segments) <= JF_MAX_SEGMENTS:
         raise ValueError("conditioning_rows: 1..%d segments" % JF_MAX_SEGMENTS)
-    dev = require_device(*[t for t, _ in segments])
+    dev = require_device(*[t for t, _ in segments], out)
     segments, width = _segments(segments, B, dtype, "conditioning_rows")
-    out = torch.empty((B, width), dtype=dtype, device=device)
+    if out is None:
+        out = torch.empty((B, width), dtype=dtype, device=device)
+    elif out.shape != (B, width) or out.dtype != dtype or (width > 1 and out.stride(1) != 1):
+        raise ValueError("conditioning_rows: out must be a (%d, %d) %s tensor with unit column stride" % (B, width, dtype))
     _launch("jf_conditioning_rows" + _suffix(out), "", (_segment_array(segments), len(segments), B, _ptr(out), out.stride(0)), dev)
     return out
 

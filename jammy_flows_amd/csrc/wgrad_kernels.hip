@@ -381,10 +381,10 @@ static void wgrad_go(const T* g, int64_t gs, const T* in, int64_t is, int64_t B,
 template <typename T>
 static int wgrad(const T* g, int64_t gs, const T* in, int64_t is, int64_t B, int32_t K, int32_t N, T* pw, T* pb, void* stream) {
     if (!g || !in || !pw || !rows_ok(B) || !width_ok(K) || !width_ok(N)) return JF_ERR_BADARG;
+    if (!wgrad_is_skinny(K, N) && K > 128) return JF_ERR_UNSUPPORTED;      // the shape rule holds for an empty batch too
     if (B == 0) return JF_OK;
     hipStream_t st = (hipStream_t)stream;
     if (wgrad_skinny<T>(g, gs, in, is, B, K, N, pw, pb, st)) return check_launch();
-    if (K > 128) return JF_ERR_UNSUPPORTED;
     const int64_t S = wgrad_splits_t<T>(B, N);
     const int kt = (K + Mfma<T>::MT - 1) / Mfma<T>::MT;        // f32: 1..4, f64: 1..8
     const bool two = wgrad_na<T>(N) == 2;

@@ -54,6 +54,28 @@ def test_tanh_fast_float64_absolute_accuracy():
     assert (got.abs() <= 1.0).all() and (torch.sign(got) == torch.sign(x)).all()
 
 
+def test_tanh_fast_float32_absolute_accuracy():
+    """tanh_fast = 1 - 2 rcp(exp(2x) + 1) on v_exp_f32 / v_rcp_f32 against float64 tanh.  Bar 1e-6 (tests/dense_bars.py: the worst case with
+    the instructions' documented 1 ulp is 5.3e-7 -- exponent-argument rounding 0.45 2^-23, exp 0.5 2^-23, rounding of E + 1 2 2^-24, rcp
+    2 2^-23, final subtraction 2^-24); a measured maximum above 5.3e-7 would mean that the 1-ulp figures do not hold."""
+    g = torch.Generator(device="cpu").manual_seed(2)
+    x = torch.cat([torch.empty(1 << 20, dtype=torch.float32).uniform_(-25.0, 25.0, generator=g),
+                   torch.empty(1 << 18, dtype=torch.float32).uniform_(-1e-6, 1e-6, generator=g),
+                   torch.tensor([0.0, -0.0, float("inf"), float("-inf"), 1e30, -1e30], dtype=torch.float32)]).cuda()
+    got = _hip.device_math(x, _hip.MATH_TANH_FAST)
+    err = (got.double() - torch.tanh(x.double())).abs().max().item()
+    print("tanh_fast float32: max absolute error %.3e (derived worst case 5.3e-7, bar 1e-6)" % err)
+    assert err < 1e-6
+    assert torch.isnan(_hip.device_math(torch.tensor([float("nan")], dtype=torch.float32).cuda(), _hip.MATH_TANH_FAST)).all()
+    assert (got.abs() <= 1.0).all()
+    assert (got[-4:] == torch.tensor([1.0, -1.0, 1.0, -1.0], device="cuda")).all()                   # saturation at +-inf and +-1e30
+    big = x.abs() >= 10.0
+    assert (got[big] == torch.sign(x[big])).all()                                                    # 1 - tanh(10) = 4e-9 < 2^-25
+    # sign: exact wherever |tanh| exceeds the absolute error; below it the result may be a signed zero or a rounding residue of either sign
+    clear = x.abs() > 1e-6
+    assert (torch.sign(got[clear]) == torch.sign(x[clear])).all()
+
+
 def test_log_fast_and_rcp_float64():
     g = torch.Generator(device="cpu").manual_seed(3)
     x = torch.exp(torch.empty(1 << 20, dtype=torch.float64).uniform_(-700.0, 700.0, generator=g)).cuda()
