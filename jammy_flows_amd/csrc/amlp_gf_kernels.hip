@@ -265,14 +265,14 @@ __global__ void __launch_bounds__(AG_THREADS) amlp_gf_kernel(const AgArgs<T> a) 
 template <typename T> static int ag_launch(const AgArgs<T>& a, int D, hipStream_t st) {
     const size_t elems = (size_t)(a.V1 ? a.r1 * a.K1 + a.H * a.r1 : a.H * a.K1) + a.H + (size_t)a.r2 * a.H + (size_t)a.N * (a.r2 | 1) + a.N;
     const size_t lds = elems * sizeof(T);
-    if (lds > 160 * 1024) return JF_ERR_UNSUPPORTED;
+    if (lds > JF_LDS_WG_MAX) return JF_ERR_UNSUPPORTED;
     const int G = D <= 4 ? 4 : 8;
     const bool small = a.r2 <= 8 && a.r1 <= 8;
     const unsigned grid = (unsigned)((a.B + AG_THREADS / G - 1) / (AG_THREADS / G));
 #define JF_AG_GO(G_, RM_)                                                                                                      \
     {                                                                                                                          \
         auto k = a.params_out ? amlp_gf_kernel<T, G_, RM_, true> : amlp_gf_kernel<T, G_, RM_, false>;                            \
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);    \
+        allow_lds(k, lds);                                                                                                     \
         jf::launch(k, dim3(grid), dim3(AG_THREADS), lds, st, a);                                                         \
     }
     if (G == 4) { if (small) JF_AG_GO(4, 8) else JF_AG_GO(4, 16) }
@@ -295,9 +295,9 @@ static int amlp2(const T* in, int64_t in_stride, const T* V1, const T* U1, const
     a.params_out = out; a.pos = out_stride;
     if constexpr (sizeof(T) == 8) {                                // float64, ranks <= 8: matrix-core version (jf_amlp_mfma.h)
         const size_t lds = am_lds_mlp_only(K1, H, V1 != nullptr, N) * sizeof(T);
-        if (r2 <= AM_R && (!V1 || r1 <= AM_R) && H % 16 == 0 && lds <= 160 * 1024) {
+        if (r2 <= AM_R && (!V1 || r1 <= AM_R) && H % 16 == 0 && lds <= JF_LDS_WG_MAX) {
             auto k = amlp2_mfma_kernel<AgArgs<T>>;
-            if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            allow_lds(k, lds);
             jf::launch(k, dim3((unsigned)((B + am_rows(AM_THREADS) - 1) / am_rows(AM_THREADS))), dim3(AM_THREADS), lds, (hipStream_t)stream, a);
             return check_launch();
         }
@@ -346,10 +346,10 @@ static int amlp_gf_chain_inv(const T* in, int64_t in_stride, const T* V1, const 
         // float64 with ranks <= 8: the whole block as a chain of v_mfma_f64_16x16x4 products (jf_amlp_mfma.h) -- same arithmetic, 16x less LDS
         // traffic; everything else (float32, larger ranks, odd hidden widths) stays on amlp_gf_kernel
         const size_t lds = am_lds_doubles(K1, H, V1 != nullptr, n_layers) * sizeof(T);
-        if (r2 <= AM_R && (!V1 || r1 <= AM_R) && H % 16 == 0 && lds <= 160 * 1024) {
+        if (r2 <= AM_R && (!V1 || r1 <= AM_R) && H % 16 == 0 && lds <= JF_LDS_WG_MAX) {
             auto k = amlp_gf_mfma_kernel<AgArgs<T>, FWD>;
             constexpr int NT = FWD ? AM_THREADS_FWD : AM_THREADS, ROWS = am_rows(NT);
-            if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            allow_lds(k, lds);
             jf::launch(k, dim3((unsigned)((B + ROWS - 1) / ROWS)), dim3(NT), lds, (hipStream_t)stream, a);
             return check_launch();
         }
@@ -368,13 +368,13 @@ static int lowrank_gf_chain_inv(const double* t2, int64_t t2s, const double* U2,
     const int col = ag_make_layers<double>(layers, n_layers, D, a.L);
     if (col < 0) return col;
     const size_t lds = (size_t)n_layers * (AM_TILES * 2 * 64 + AM_TILES * 16) * sizeof(double);
-    if (lds > 160 * 1024) return JF_ERR_UNSUPPORTED;
+    if (lds > JF_LDS_WG_MAX) return JF_ERR_UNSUPPORTED;
     if (B == 0) return JF_OK;
     a.t2 = t2; a.t2s = t2s; a.U2 = U2; a.b2 = b2; a.r2 = r2; a.x = x; a.xs = xs; a.ld_in = ld_in; a.B = B; a.D = D; a.n_layers = n_layers;
     a.x_out = x_out; a.xos = xos; a.ld_out = ld_out; a.blp_in = blp_in; a.blp_out = blp_out; a.aux = aux; a.status = status;
     auto k = lr_gf_fwd_kernel<LrFwdArgs<double>>;
     static LdsAttrOnce attr;
-    if (lds > 48 * 1024) attr.set((const void*)k, (int)lds);
+    attr.set((const void*)k, (int)JF_LDS_WG_MAX);                  // the bound checked above: lds grows with n_layers
     constexpr int ROWS = am_rows(AM_THREADS);
     jf::launch(k, dim3((unsigned)((B + ROWS - 1) / ROWS)), dim3(AM_THREADS), lds, (hipStream_t)stream, a);
     return check_launch();
@@ -391,7 +391,7 @@ static int lowrank_gf_chain_inv_bwd(const double* t2, int64_t t2s, const double*
     const int col = ag_make_layers<double>(layers, n_layers, D, red.L);
     if (col < 0) return col;
     const int n_wg = lr_n_wg(B);
-    const size_t lds = (size_t)(LR_TILES * 2 * 64 + LR_TILES * 16 + LR_PSZ + LR_NW * 2 * 16 * 17) * sizeof(double);
+    constexpr size_t lds = (size_t)(LR_TILES * 2 * 64 + LR_TILES * 16 + LR_PSZ + LR_NW * 2 * 16 * 17) * sizeof(double);
     static LdsAttrOnce attr;
     attr.set((const void*)lr_gf_bwd_layer_kernel, (int)lds);
     for (int l = 0; l < n_layers; ++l) {
@@ -426,6 +426,12 @@ static int lowrank_head(const double* in, int64_t is, const double* V1, const do
     return check_launch();
 }
 
+// dynamic LDS of lrm_head_bwd_kernel: grows with H and KT, and stays inside a workgroup's limit for every shape lrm_shape_ok admits
+constexpr size_t lrm_bwd_lds(int H, int KT) {
+    return ((size_t)(H / 16) * 2 * 64 + (size_t)(H / 4) * 64 + (size_t)KT * 2 * 64 + lrm_psz(H, KT) + (size_t)LRM_NW * 2 * 16 * 17) * sizeof(double);
+}
+static_assert(lrm_bwd_lds(AG_HMAX, LRM_KT) <= JF_LDS_WG_MAX, "lowrank_head_bwd: the widest admitted shape must fit a workgroup's LDS");
+
 static int lowrank_head_bwd(const double* in, int64_t is, const double* V1, const double* U1, const double* V2, int64_t B, int32_t K1, int32_t H,
                             int32_t r1, int32_t r2, const double* t1, const double* h, const double* g_t2, int64_t gs, double* g_c, int64_t gcs,
                             double* g_V1, double* g_U1, double* g_b1, double* g_V2, double* workspace, void* stream) {
@@ -435,13 +441,13 @@ static int lowrank_head_bwd(const double* in, int64_t is, const double* V1, cons
     LrmBwdArgs a{};
     a.in = in; a.in_stride = is; a.V1 = V1; a.U1 = U1; a.V2 = V2; a.K1 = K1; a.H = H; a.r1 = r1; a.r2 = r2; a.B = B; a.n_row_tiles = (B + 15) / 16;
     a.t1 = t1; a.h = h; a.g_t2 = g_t2; a.gs = gs; a.g_c = g_c; a.gcs = gcs; a.partial = workspace;
-    const size_t lds = ((size_t)(H / 16) * 2 * 64 + (size_t)(H / 4) * 64 + (size_t)KT * 2 * 64 + psz + (size_t)LRM_NW * 2 * 16 * 17) * sizeof(double);
-    static LdsAttrOnce attr1, attr2;
+    const size_t lds = lrm_bwd_lds(H, KT);
+    static LdsAttrOnce attr1, attr2;                               // (the bound, not this call's lds: it grows with H and KT)
     if (KT == 1) {
-        attr1.set((const void*)lrm_head_bwd_kernel<1>, (int)lds);
+        attr1.set((const void*)lrm_head_bwd_kernel<1>, (int)JF_LDS_WG_MAX);
         jf::launch(lrm_head_bwd_kernel<1>, dim3((unsigned)n_wg), dim3(LRM_NW * 64), lds, (hipStream_t)stream, a);
     } else {
-        attr2.set((const void*)lrm_head_bwd_kernel<2>, (int)lds);
+        attr2.set((const void*)lrm_head_bwd_kernel<2>, (int)JF_LDS_WG_MAX);
         jf::launch(lrm_head_bwd_kernel<2>, dim3((unsigned)n_wg), dim3(LRM_NW * 64), lds, (hipStream_t)stream, a);
     }
     LrmReduceArgs red{};

@@ -422,7 +422,7 @@ static int cb_pack(const float* W2, int64_t w2s, int32_t H, int32_t D, int32_t n
     jf::launch(cs_absmax_kernel, dim3(1), dim3(1024), 0, st, W2, w2s, col, (int)H,
                        reinterpret_cast<float*>(a.out + (size_t)n_layers * CB_KSTEPS * CB_T_BYTES));
     jf::launch(cb_pack_kernel, dim3((threads + 255) / 256), dim3(256), 0, st, a);
-    return hipPeekAtLastError() == hipSuccess ? JF_OK : JF_ERR_LAUNCH;
+    return check_launch();
 }
 
 static int cb_chain(const float* in, int64_t in_stride, const float* W1, int64_t w1s, const float* b1, const void* packed, const void* packedT,
@@ -449,11 +449,11 @@ static int cb_chain(const float* in, int64_t in_stride, const float* W1, int64_t
     a.z = z; a.zs = zs; a.aux = aux; a.B = B; a.D = D; a.n_layers = n_layers;
     a.g_xout = g_xout; a.gxos = gxos; a.g_ld = g_ld; a.g_blp = g_blp; a.g_x = g_x; a.gxs = gxs; a.g_pp = g_pp; a.gpps = gpps;
     a.h_out = h_out; a.hs = hs; a.g_h = g_h; a.ghs = ghs; a.g_absmax = g_absmax;
-    const size_t lds = 2 * CB_BUF;                                 // (phase 1's scratch, <= 22.8 KB at K1 = 28, fits buffer 1)
+    constexpr size_t lds = 2 * CB_BUF;                               // (phase 1's scratch, <= 22.8 KB at K1 = 28, fits buffer 1)
     static LdsAttrOnce attr;
     attr.set((const void*)cond_gf_split_bwd_kernel, (int)lds);
     jf::launch(cond_gf_split_bwd_kernel, dim3((unsigned)((B + CS_ROWS1 - 1) / CS_ROWS1)), dim3(256), lds, (hipStream_t)stream, a);
-    return hipPeekAtLastError() == hipSuccess ? JF_OK : JF_ERR_LAUNCH;
+    return check_launch();
 }
 
 }  // namespace jf

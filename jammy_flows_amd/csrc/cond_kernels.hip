@@ -261,7 +261,7 @@ __global__ void __launch_bounds__(256, 2) cond_gf_chain_kernel(const CondArgs<T>
 // ----------------------------------------------------------------------------------------------------------
 template <typename T, int JH> static int cond_launch(const CondArgs<T>& a, size_t lds, hipStream_t st) {
     auto k = cond_gf_chain_kernel<T, JH>;
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    allow_lds(k, lds);
     jf::launch(k, dim3((unsigned)((a.B + CG_ROWS - 1) / CG_ROWS)), dim3(256), lds, st, a);
     return check_launch();
 }
@@ -314,7 +314,7 @@ static int cond_gf_chain_inv(const T* in, int64_t in_stride, const T* W1, int64_
     const size_t chunk = (size_t)CG_CHUNK * CgCfg<T>::LDW + CG_CHUNK;
     if (phase1 > chunk) return JF_ERR_UNSUPPORTED;
     const size_t lds = (chunk + (size_t)4 * 16 * a.tile_stride) * sizeof(T);
-    if (lds > 160 * 1024) return JF_ERR_UNSUPPORTED;
+    if (lds > JF_LDS_WG_MAX) return JF_ERR_UNSUPPORTED;
     const int tiles = (H + 15) / 16;
     if (tiles <= 2) return cond_launch<T, 2>(a, lds, (hipStream_t)stream);
     if (tiles <= 4) return cond_launch<T, 4>(a, lds, (hipStream_t)stream);

@@ -64,16 +64,12 @@ static int cond_mchain(const T* in, int64_t in_stride, const T* W1, int64_t w1s,
     //  8 more elements behind the bias for the workgroup's absmax reduction)
     const size_t lds = ((size_t)CM_HMAX * ldk + CM_HMAX + (size_t)np * (CM_HMAX + 1) + np + 8 + (size_t)NT * ldk + (size_t)NT * a.tile_stride +
                         (size_t)NT * a.tab) * sizeof(T);
-    if (lds > 160 * 1024) return JF_ERR_UNSUPPORTED;
+    if (lds > JF_LDS_WG_MAX) return JF_ERR_UNSUPPORTED;
     auto k = cond_mchain_kernel<T, Fam, NT, FWD>;
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    allow_lds(k, lds);
     // one resident round of workgroups (occupancy x CUs, at most one per row tile)
-    int dev = 0, cus = 256, per_cu = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, NT, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-    const int64_t n_tiles = (B + NT - 1) / NT, resident = (int64_t)cus * per_cu;
-    jf::launch(k, dim3((unsigned)(n_tiles < resident ? n_tiles : resident)), dim3(NT), lds, (hipStream_t)stream, a);
+    const int64_t grid = resident_grid((B + NT - 1) / NT, occupancy_per_cu(k, NT, lds, 1));
+    jf::launch(k, dim3((unsigned)grid), dim3(NT), lds, (hipStream_t)stream, a);
     return check_launch();
 }
 

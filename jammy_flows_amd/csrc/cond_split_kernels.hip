@@ -128,7 +128,7 @@ static int cs_pack(const float* W2, int64_t w2s, const float* b2, int32_t H, int
     } else {
         jf::launch(cs_pack_kernel<3>, dim3((threads + 255) / 256), dim3(256), 0, st, a);
     }
-    return hipPeekAtLastError() == hipSuccess ? JF_OK : JF_ERR_LAUNCH;
+    return check_launch();
 }
 
 template <bool FWD, bool SAVE, int NP>
@@ -152,7 +152,7 @@ static int cs_launch(const CsArgs& a, int64_t B, hipStream_t st) {
     const bool two = force_rg ? force_rg == 2 : (!FWD && B >= (int64_t)CS_ROWS1 * 2 * 1024);
     if (two) jf::launch((cond_gf_split_kernel<2, FWD, SAVE, NP>), dim3((unsigned)((B + 2 * CS_ROWS1 - 1) / (2 * CS_ROWS1))), dim3(256), lds_of(2), st, a);
     else jf::launch((cond_gf_split_kernel<1, FWD, SAVE, NP>), dim3((unsigned)((B + CS_ROWS1 - 1) / CS_ROWS1)), dim3(256), lds_of(1), st, a);
-    return hipPeekAtLastError() == hipSuccess ? JF_OK : JF_ERR_LAUNCH;
+    return check_launch();
 }
 
 template <bool FWD>

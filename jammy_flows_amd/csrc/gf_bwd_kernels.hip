@@ -876,14 +876,10 @@ static int gb_launch(GfBwdArgs<T> a, bool bcast, hipStream_t st) {
             return check_launch();
         }
         auto k = gf_chain_bwd_kernel<T, G, true>;
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        allow_lds(k, lds);
         // one resident round of workgroups takes all tiles (grid stride): each pays the prologue / epilogue once, no tail round
-        int dev = 0, cus = 256, occ = 1;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)k, GB_NT, lds) != hipSuccess || occ < 1) occ = 1;
-        int64_t active = (int64_t)cus * occ;
-        if (active > blocks) active = blocks;
+        // (the grid stays `blocks`, one per partial row: the workgroups past `active` write a zero row)
+        int64_t active = resident_grid(blocks, occupancy_per_cu(k, GB_NT, lds, 1));
         if (active > n_tiles) active = n_tiles < 1 ? 1 : n_tiles;
         a.active_blocks = (int)active;
         a.tiles_per_block = (int)((n_tiles + active - 1) / active);
@@ -893,7 +889,7 @@ static int gb_launch(GfBwdArgs<T> a, bool bcast, hipStream_t st) {
         const bool direct = (size_t)a.D * sizeof(T) >= 32;
         const size_t lds = (size_t)(direct ? 1 : 2) * (64 / G) * a.tile_stride * sizeof(T);
         auto k = direct ? gf_chain_bwd_kernel<T, G, false, true> : gf_chain_bwd_kernel<T, G, false, false>;
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        allow_lds(k, lds);
         jf::launch(k, dim3((unsigned)((a.B + 64 / G - 1) / (64 / G))), dim3(64), lds, st, a);
     }
     return check_launch();
@@ -922,9 +918,9 @@ static int gf_chain_inv_bwd(const T* x, int64_t xs, const T* params, int64_t ps,
         static const int dual_replay = getenv("JF_G_BWD_DUAL") ? atoi(getenv("JF_G_BWD_DUAL")) : 0;
         if (dual_replay <= 0) return gfx_chain_rev_launch<T>(a, bcast, ps, blocks, tiles, stream);
         const size_t lds = (size_t)JF_MAX_D_GF * GX_THREADS * sizeof(Dual<T>) + 16 * sizeof(T) + (size_t)GX_THREADS * a.spline_tab * sizeof(Dual<T>);
-        if (lds > 160 * 1024) return JF_ERR_UNSUPPORTED;
+        if (lds > JF_LDS_WG_MAX) return JF_ERR_UNSUPPORTED;
         auto k = gfx_chain_bwd_kernel<T>;
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        allow_lds(k, lds);
         jf::launch(k, dim3((unsigned)blocks), dim3(GX_THREADS), lds, (hipStream_t)stream, a, bcast ? (int64_t)0 : ps, tiles);
         return check_launch();
     }

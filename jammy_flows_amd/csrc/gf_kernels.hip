@@ -419,34 +419,26 @@ template <typename T> static int fill_args(GfChainArgs<T>& a, const T* params, i
     return JF_OK;
 }
 
-// resident workgroups of a broadcast kernel on the whole device (occupancy x CUs), queried once per kernel
-template <typename K> static int resident_blocks(K k, size_t lds_bytes) {
-    int dev = 0, cus = 256, per_cu = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, 256, lds_bytes) != hipSuccess || per_cu < 1) per_cu = 4;
-    return cus * per_cu;
+// A broadcast kernel runs as ONE wave of workgroups: every workgroup derives the parameters once and walks ceil(tiles / resident) row tiles of
+// `rows_per_tile` rows, so the grid has no partially filled last round (a 2.3-round grid idles a quarter of the chip in its tail).  resident =
+// the kernel's occupancy x the CUs of the CURRENT device.
+template <typename T, typename K> static int launch_resident(K k, int rows_per_tile, GfChainArgs<T> a, size_t lds_bytes, hipStream_t st) {
+    allow_lds(k, lds_bytes);
+    int resident = device_cus() * occupancy_per_cu(k, 256, lds_bytes, 4);
+    if (resident < 1) resident = 1;
+    const int64_t n_tiles = (a.B + rows_per_tile - 1) / rows_per_tile;
+    const int64_t tpb = (n_tiles + resident - 1) / resident;
+    a.tiles_per_block = (int)(tpb < 1 ? 1 : tpb);
+    jf::launch(k, dim3((unsigned)((n_tiles + a.tiles_per_block - 1) / a.tiles_per_block)), dim3(256), lds_bytes, st, a);
+    return check_launch();
 }
 
 template <typename T, int G, bool FWD> static int launch_g(GfChainArgs<T> a, bool bcast, size_t lds_bytes, hipStream_t st) {
-    if (bcast) {
-        auto k = gf_chain_kernel<T, G, true, FWD>;
-        if (lds_bytes > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        // one wave of workgroups: every workgroup derives the parameters once and walks ceil(tiles / resident) row tiles, so the grid has
-        // no partially filled last round (a 2.3-round grid idles a quarter of the chip in its tail)
-        int resident = resident_blocks(k, lds_bytes);       // for the CURRENT device; two cheap runtime queries, no cross-thread cache
-        if (resident < 1) resident = 1;
-        const int64_t n_tiles = (a.B + 256 / G - 1) / (256 / G);
-        const int64_t tpb = (n_tiles + resident - 1) / resident;
-        a.tiles_per_block = (int)(tpb < 1 ? 1 : tpb);
-        const unsigned grid = (unsigned)((n_tiles + a.tiles_per_block - 1) / a.tiles_per_block);
-        jf::launch(k, dim3(grid), dim3(256), lds_bytes, st, a);
-    } else {
-        auto k = gf_chain_kernel<T, G, false, FWD>;
-        if (lds_bytes > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        const unsigned grid = (unsigned)((a.B + 64 / G - 1) / (64 / G));
-        jf::launch(k, dim3(grid), dim3(64), lds_bytes, st, a);
-    }
+    if (bcast) return launch_resident<T>(gf_chain_kernel<T, G, true, FWD>, 256 / G, a, lds_bytes, st);
+    auto k = gf_chain_kernel<T, G, false, FWD>;
+    allow_lds(k, lds_bytes);
+    const unsigned grid = (unsigned)((a.B + 64 / G - 1) / (64 / G));
+    jf::launch(k, dim3(grid), dim3(64), lds_bytes, st, a);
     return check_launch();
 }
 
@@ -459,31 +451,12 @@ static int64_t gfbg_max_rows() {
     static const int64_t v = getenv("JF_GFB_LANE_ROWS") ? atoll(getenv("JF_GFB_LANE_ROWS")) : ((int64_t)1 << 16);
     return gfbg_forced_rows >= 0 ? gfbg_forced_rows : v;
 }
-template <typename T, int D, int G> static int launch_rows_g(GfChainArgs<T> a, size_t lds_bytes, hipStream_t st) {
-    auto k = gfbg_chain_inv_kernel<T, D, G>;
-    if (lds_bytes > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    int resident = resident_blocks(k, lds_bytes);
-    if (resident < 1) resident = 1;
-    const int64_t n_tiles = (a.B + 256 / G - 1) / (256 / G);
-    const int64_t tpb = (n_tiles + resident - 1) / resident;
-    a.tiles_per_block = (int)(tpb < 1 ? 1 : tpb);
-    jf::launch(k, dim3((unsigned)((n_tiles + a.tiles_per_block - 1) / a.tiles_per_block)), dim3(256), lds_bytes, st, a);
-    return check_launch();
-}
-
 template <typename T, int D> static int launch_rows(GfChainArgs<T> a, size_t lds_bytes, hipStream_t st) {
     if constexpr (D >= 2 && D <= 4) {
-        if (a.B < gfbg_max_rows()) return launch_rows_g<T, D, (D == 2 ? 2 : 4)>(a, lds_bytes, st);
+        constexpr int G = D == 2 ? 2 : 4;
+        if (a.B < gfbg_max_rows()) return launch_resident<T>(gfbg_chain_inv_kernel<T, D, G>, 256 / G, a, lds_bytes, st);
     }
-    auto k = gfb_chain_inv_kernel<T, D>;
-    if (lds_bytes > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    int resident = resident_blocks(k, lds_bytes);           // one wave of workgroups, as for the lane = (row, coordinate) broadcast kernel
-    if (resident < 1) resident = 1;
-    const int64_t n_tiles = (a.B + 255) / 256;
-    const int64_t tpb = (n_tiles + resident - 1) / resident;
-    a.tiles_per_block = (int)(tpb < 1 ? 1 : tpb);
-    jf::launch(k, dim3((unsigned)((n_tiles + a.tiles_per_block - 1) / a.tiles_per_block)), dim3(256), lds_bytes, st, a);
-    return check_launch();
+    return launch_resident<T>(gfb_chain_inv_kernel<T, D>, 256, a, lds_bytes, st);
 }
 
 template <typename T, bool FWD> static int launch(const GfChainArgs<T>& a, int D, bool bcast, bool ext, size_t lds_bytes, hipStream_t st) {
@@ -514,7 +487,7 @@ template <typename T, bool FWD> static int launch(const GfChainArgs<T>& a, int D
     if (ext && a.cot_in != nullptr) return JF_ERR_UNSUPPORTED;
     if (ext) {
         auto k = gfx_chain_kernel<T, FWD>;
-        if (lds_bytes > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        allow_lds(k, lds_bytes);
         jf::launch(k, dim3((unsigned)((a.B + a.group - 1) / a.group)), dim3(a.group), lds_bytes, st, a, bcast ? (int64_t)0 : a.ps);
         return check_launch();
     }

@@ -353,7 +353,7 @@ template <typename T> int64_t gfx_chain_rev_lds_bytes(const GfBwdArgs<T>& a, boo
 // row-owning lanes per wave: 64, halved while the knot tables do not fit a CU's LDS (down to 4)
 template <typename T> static int gfx_chain_rev_lanes(GfBwdArgs<T> a, bool bcast) {
     a.lanes = 64;
-    while ((size_t)gfx_chain_rev_lds_bytes<T>(a, bcast) > 160 * 1024 && a.spline_tab > 0 && a.lanes > 4) a.lanes >>= 1;
+    while ((size_t)gfx_chain_rev_lds_bytes<T>(a, bcast) > JF_LDS_WG_MAX && a.spline_tab > 0 && a.lanes > 4) a.lanes >>= 1;
     return a.lanes;
 }
 // LDS bytes of the launch with a.lanes row-owning lanes per wave; a.lanes == 0: with the lane count gfx_chain_rev_launch would choose
@@ -371,13 +371,13 @@ template <typename T> int64_t gfx_chain_rev_lds_bytes(const GfBwdArgs<T>& a, boo
 template <typename T> int gfx_chain_rev_launch(GfBwdArgs<T> a, bool bcast, int64_t ps, int64_t blocks, int64_t tiles, void* stream) {
     a.lanes = gfx_chain_rev_lanes<T>(a, bcast);                                   // fewer rows, and knot tables, per workgroup (see the kernel)
     const size_t lds = (size_t)gfx_chain_rev_lds_bytes<T>(a, bcast);
-    if (lds > 160 * 1024) return JF_ERR_UNSUPPORTED;
+    if (lds > JF_LDS_WG_MAX) return JF_ERR_UNSUPPORTED;
     if (a.lanes < 64) {
         tiles = (a.B + (GX_THREADS / 64) * a.lanes - 1) / ((GX_THREADS / 64) * a.lanes);
         if (!bcast) blocks = tiles;
     }
     auto k = gfx_chain_rev_kernel<T>;
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    allow_lds(k, lds);
     jf::launch(k, dim3((unsigned)blocks), dim3(GX_THREADS), lds, (hipStream_t)stream, a, bcast ? (int64_t)0 : ps, tiles);
     return check_launch();
 }

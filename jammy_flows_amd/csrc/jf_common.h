@@ -18,9 +18,24 @@ constexpr int64_t JF_MAX_WIDTH = 1 << 24, JF_MAX_ROWS = (int64_t)1 << 40;
 inline bool width_ok(int64_t v) { return v >= 1 && v <= JF_MAX_WIDTH; }
 inline bool rows_ok(int64_t v) { return v >= 0 && v <= JF_MAX_ROWS; }
 
+// ---------------------------------------------------------------------------------------------
+// Launch geometry.  Every entry point takes its three launch decisions from here: the dynamic-LDS opt-in (allow_lds, or LdsAttrOnce on the
+// paths where a runtime call per launch shows), the CU count of the current device (device_cus) and the size of a resident grid, whose
+// workgroups walk the tiles (resident_grid, with a fixed number of workgroups per CU or the kernel's own occupancy_per_cu).
+// ---------------------------------------------------------------------------------------------
+constexpr size_t JF_LDS_WG_MAX = 160 * 1024;       // what one workgroup may ask for on gfx950
+constexpr size_t JF_LDS_NO_OPT_IN = 48 * 1024;     // above this a launch needs hipFuncAttributeMaxDynamicSharedMemorySize raised first
+
+// the opt-in for THIS launch's size, at every launch (one runtime call); nothing to do at or below JF_LDS_NO_OPT_IN
+template <typename K> inline void allow_lds(K kernel, size_t lds) {
+    if (lds > JF_LDS_NO_OPT_IN) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+}
+
 // hipFuncAttributeMaxDynamicSharedMemorySize is an attribute of a kernel PER DEVICE: a `static bool` guard sets it on the first device a process
 // touches only, and a later launch on another GPU fails.  One of these per call site: a bit per device, set once, safe from several
-// host threads (at worst two threads set the same value).
+// host threads (at worst two threads set the same value).  Because the first call's size stays, `bytes` is a constant of the KERNEL (its
+// compile-time size, or the bound its entry point enforces, JF_LDS_WG_MAX), never a size computed from the call's arguments: a later, larger
+// call would be refused by the runtime.
 struct LdsAttrOnce {
     std::atomic<uint64_t> done{0};
     void set(const void* fn, int bytes) {
@@ -31,6 +46,28 @@ struct LdsAttrOnce {
         if (known) done.fetch_or(1ull << dev, std::memory_order_release);
     }
 };
+
+// CUs of the CURRENT device (256 where the query fails): two cheap runtime queries at every call and no cache, since a process may drive
+// several GPUs from several threads
+inline int device_cus() {
+    int dev = 0, cus = 256;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    return cus;
+}
+
+// workgroups of `kernel` that one CU holds at this block size and dynamic LDS; `fallback` where the query fails or finds none
+template <typename K> inline int occupancy_per_cu(K kernel, int threads, size_t lds, int fallback) {
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kernel, threads, lds) != hipSuccess || per_cu < 1) per_cu = fallback;
+    return per_cu;
+}
+
+// a resident set of workgroups walks the tiles: at most `per_cu` workgroups on each CU of the current device
+inline int64_t resident_grid(int64_t tiles, int64_t per_cu) {
+    const int64_t resident = (int64_t)device_cus() * per_cu;
+    return tiles < resident ? tiles : resident;
+}
 
 
 // ---------------------------------------------------------------------------------------------

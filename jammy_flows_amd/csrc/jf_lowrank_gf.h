@@ -32,7 +32,8 @@ constexpr int LR_NW = 8;                        // waves of a backward workgroup
 constexpr int LR_RS = AM_R + 1;                  // accumulator row: r2 <= 8 rank columns + the bias column
 constexpr int LR_TILES = AG_HH + 1 + 2 * AG_K;   // tiles of a layer in the BACKWARD kernel's order (lr_col)
 constexpr int LR_PSZ = LR_TILES * 16 * LR_RS;    // doubles of one layer's partial image
-constexpr int LR_MAX_WG = 256;                   // one resident workgroup per CU of an MI355X
+constexpr int LR_MAX_WG = 256;                   // one resident workgroup per CU of an MI355X: a fixed count, not jf::device_cus(), because it
+                                                 // sizes the workspace the caller allocates (jf_lowrank_gf_workspace_doubles)
 constexpr int LR_AUX = 5;                        // per layer and coordinate: rotated input, cdf, sf, pdf sums (normalised), 1 / sum of weights
 
 template <typename T> struct LrFwdArgs {

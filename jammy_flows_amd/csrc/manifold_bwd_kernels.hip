@@ -991,44 +991,30 @@ static int mchain_bwd(const T* x, int64_t xs, const T* params, int64_t ps, int32
             lds = tile_elems * sizeof(T) + (size_t)64 * (size_t)(a.tab + a.rot_max) * sizeof(Dual<T>) + (size_t)a.rows * (size_t)a.scratch * sizeof(T) + accp;
         } else
         lds = ((size_t)(a.bcast ? 1 : a.rows) * a.tile_stride + tabs + (size_t)a.rows * a.scratch) * sizeof(DualN<T, 1>) + accp;
-        if (lds <= 160 * 1024 || a.rows == 4) break;
+        if (lds <= JF_LDS_WG_MAX || a.rows == 4) break;
         a.rows >>= 1;
     }
-    if (lds > 160 * 1024) return JF_ERR_UNSUPPORTED;
+    if (lds > JF_LDS_WG_MAX) return JF_ERR_UNSUPPORTED;
+    // staged 'v' and generic kernel alike: one workgroup per tile of a.rows rows; broadcast parameters: a resident set of workgroups walks the
+    // tiles (four per CU)
+    const int64_t tiles = (B + a.rows - 1) / a.rows, grid = a.bcast ? resident_grid(tiles, 4) : tiles;
     if constexpr (std::is_same<Fam, VFam>::value) {
         if (staged) {
             auto kv = a.v_dual ? vchain_bwd_kernel<T, 1, 1, true> : vchain_bwd_kernel<T, 1, 1, false>;
-            if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kv, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            int64_t grid = (B + a.rows - 1) / a.rows;
-            if (a.bcast) {                                         // a resident set of workgroups walks the tiles (four per CU)
-                int dev = 0, cus = 256;
-                (void)hipGetDevice(&dev);
-                (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-                if (grid > (int64_t)cus * 4) grid = (int64_t)cus * 4;
-            }
+            allow_lds(kv, lds);
             jf::launch(kv, dim3((unsigned)grid), dim3(64), lds, (hipStream_t)stream, a);
             return check_launch();
         }
     }
-    // generic kernel: one workgroup per 64-row tile; broadcast parameters: a resident set of workgroups walks the tiles (four per CU)
-    auto generic_grid = [&]() -> int64_t {
-        const int64_t tiles = (B + a.rows - 1) / a.rows;
-        if (!a.bcast) return tiles;
-        int dev = 0, cus = 256;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        const int64_t resident = (int64_t)cus * 4;
-        return tiles < resident ? tiles : resident;
-    };
     if (wide) {
         auto k4 = mchain_bwd_kernel<T, Fam, NW>;
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k4, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        jf::launch(k4, dim3((unsigned)generic_grid()), dim3(64), lds, (hipStream_t)stream, a);
+        allow_lds(k4, lds);
+        jf::launch(k4, dim3((unsigned)grid), dim3(64), lds, (hipStream_t)stream, a);
         return check_launch();
     }
     auto k = mchain_bwd_kernel<T, Fam, 1>;
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    jf::launch(k, dim3((unsigned)generic_grid()), dim3(64), lds, (hipStream_t)stream, a);
+    allow_lds(k, lds);
+    jf::launch(k, dim3((unsigned)grid), dim3(64), lds, (hipStream_t)stream, a);
     return check_launch();
 }
 

@@ -175,12 +175,12 @@ static int mchain(const T* x, int64_t xs, const T* ld_in, const T* params, int64
     size_t lds = 0;
     for (;;) {
         lds = ((size_t)(a.bcast ? 1 : a.rows) * a.tile_stride + (size_t)(a.shared_tab ? 1 : a.rows) * a.tab + (size_t)a.rows * a.scratch) * sizeof(T);
-        if (lds <= 160 * 1024 || a.rows == 8) break;
+        if (lds <= JF_LDS_WG_MAX || a.rows == 8) break;
         a.rows >>= 1;
     }
-    if (lds > 160 * 1024) return JF_ERR_UNSUPPORTED;
+    if (lds > JF_LDS_WG_MAX) return JF_ERR_UNSUPPORTED;
     auto k = mchain_kernel<T, Fam, FWD>;
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    allow_lds(k, lds);
     jf::launch(k, dim3((unsigned)((B + a.rows - 1) / a.rows)), dim3(64), lds, (hipStream_t)stream, a);
     return check_launch();
 }

@@ -306,14 +306,10 @@ static int mchain_rev(const T* x, int64_t xs, const T* params, int64_t ps, int32
     a.shared = (adj_has_shared<Adj>::value && a.bcast && all_hand && col > 0) ? 1 : 0;
     size_t lds = 0;
     auto k = mchain_rev_kernel<T, Fam, Adj>;
-    int dev = 0, cus = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     if constexpr (adj_has_shared<Adj>::value) {
         if (a.shared) {
             lds = 16 + ((size_t)2 * a.tile_stride + (size_t)2 * n_layers * a.scr) * sizeof(T);
-            int64_t grid = (B + REV_SHARED_THREADS - 1) / REV_SHARED_THREADS;
-            if (grid > (int64_t)cus * 2) grid = (int64_t)cus * 2;       // resident workgroups walk the tiles
+            const int64_t grid = resident_grid((B + REV_SHARED_THREADS - 1) / REV_SHARED_THREADS, 2);   // resident workgroups walk the tiles
             jf::launch(mchain_rev_shared_kernel<T, Fam, Adj>, dim3((unsigned)grid), dim3(REV_SHARED_THREADS), lds, (hipStream_t)stream, a);
             return check_launch();
         }
@@ -326,13 +322,12 @@ static int mchain_rev(const T* x, int64_t xs, const T* params, int64_t ps, int32
         if (lds <= 64 * 1024 && a.rows <= 32) break;
         a.rows >>= 1;
     }
-    if (lds > 160 * 1024) return JF_ERR_UNSUPPORTED;
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (lds > JF_LDS_WG_MAX) return JF_ERR_UNSUPPORTED;
+    allow_lds(k, lds);
     int64_t grid = (B + a.rows - 1) / a.rows;
-    if (a.bcast) {                                                 // a resident set of workgroups walks the tiles
+    if (a.bcast) {                                                 // a resident set of workgroups walks the tiles: as many as a CU's 160 KB of LDS hold, 1 .. 8
         const int64_t per_cu = lds > 0 ? (int64_t)(160 * 1024 / lds) : 8;
-        const int64_t resident = (int64_t)cus * (per_cu < 1 ? 1 : (per_cu > 8 ? 8 : per_cu));
-        if (grid > resident) grid = resident;
+        grid = resident_grid(grid, per_cu < 1 ? 1 : (per_cu > 8 ? 8 : per_cu));
     }
     jf::launch(k, dim3((unsigned)grid), dim3(64), lds, (hipStream_t)stream, a);
     return check_launch();

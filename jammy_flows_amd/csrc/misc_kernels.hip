@@ -277,7 +277,7 @@ template <typename T> static int slab_sum(const T* a, int64_t na, T* out_a, cons
     if (map && chunks != 1) return JF_ERR_BADARG;
     jf::launch(slab_sum_kernel<T>, dim3((unsigned)((na + nb + 31) / 32), (unsigned)chunks), dim3(256), 0, (hipStream_t)stream, a, na, out_a, b, nb,
                        out_b, (int)S, (int)chunk, map);
-    return hipPeekAtLastError() == hipSuccess ? JF_OK : JF_ERR_LAUNCH;
+    return check_launch();
 }
 
 template <typename T> static int tanh_bwd(const T* g, const T* y, int64_t n, T* out, void* stream) {

@@ -331,7 +331,7 @@ static int ci_pack(const double* W2, int64_t w2s, const double* b2, int32_t H, i
     hipStream_t st = (hipStream_t)stream;
     if (S == 6) jf::launch(ci_pack_kernel<6>, dim3((threads + 255) / 256), dim3(256), 0, st, a);
     else jf::launch(ci_pack_kernel<5>, dim3((threads + 255) / 256), dim3(256), 0, st, a);
-    return hipPeekAtLastError() == hipSuccess ? JF_OK : JF_ERR_LAUNCH;
+    return check_launch();
 }
 
 template <int S> static int ci_launch(const CiArgs& a, hipStream_t st) {
@@ -343,7 +343,7 @@ template <int S> static int ci_launch(const CiArgs& a, hipStream_t st) {
     static LdsAttrOnce attr;                                       // per template instance (S) and per device
     attr.set((const void*)mlp2_i8_kernel<S>, 128 * 1024);
     jf::launch((mlp2_i8_kernel<S>), dim3((unsigned)((a.B + CI_ROWS - 1) / CI_ROWS)), dim3(CI_THREADS), lds, st, a);
-    return hipPeekAtLastError() == hipSuccess ? JF_OK : JF_ERR_LAUNCH;
+    return check_launch();
 }
 
 static int ci_mlp2(const double* in, int64_t in_stride, const double* W1, int64_t w1s, const double* b1, const void* packed, int64_t B, int32_t K1,

@@ -433,16 +433,9 @@ static int mlp2_launch(const T* in, int64_t in_stride, const T* W1, int64_t w1_s
     // 16-byte result stores need 16-byte aligned rows
     const bool vecrow = (out_stride % Vec16<T>::N == 0) && ((reinterpret_cast<uintptr_t>(out) & 15u) == 0);
     auto k = vecrow ? mlp2_kernel<T, JH, TN, true, L1> : mlp2_kernel<T, JH, TN, false, L1>;
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    allow_lds(k, lds);
     int64_t grid = (B + BMR - 1) / BMR;
-    if (N <= TN * MT) {                                      // single W2 tile: resident workgroups walk the row tiles
-        int dev = 0, cus = 256, per_cu = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, 256, lds) != hipSuccess || per_cu < 1) per_cu = 2;
-        const int64_t resident = (int64_t)cus * per_cu;
-        if (grid > resident) grid = resident;
-    }
+    if (N <= TN * MT) grid = resident_grid(grid, occupancy_per_cu(k, 256, lds, 2));   // single W2 tile: resident workgroups walk the row tiles
     jf::launch(k, dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream, in, in_stride, W1, w1_stride, b1, W2, w2_stride, b2, B,
                        (int)K1, (int)H, (int)N, out, out_stride, act);
     return check_launch();

@@ -167,14 +167,9 @@ int mlp2_narrow_f32(const float* in, int64_t is, const float* W1, int64_t w1s, c
     MnArgs a{in, is, W1, w1s, b1, W2, w2s, b2, B, K1, H, N, out, os, 0};
     const bool al16 = (reinterpret_cast<uintptr_t>(out) & 15u) == 0, al8 = (reinterpret_cast<uintptr_t>(out) & 7u) == 0;
     a.vec_out = (N % 4 == 0 && os % 4 == 0 && al16) ? 4 : (N % 2 == 0 && os % 2 == 0 && al8) ? 2 : 1;
-    int dev = 0, cus = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     auto go = [&](auto kernel) {
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0) != hipSuccess || per_cu < 1) per_cu = 2;
-        const int64_t wg_tiles = (B + 63) / 64, resident = (int64_t)cus * per_cu;
-        jf::launch(kernel, dim3((unsigned)(wg_tiles < resident ? wg_tiles : resident)), dim3(256), 0, (hipStream_t)stream, a);
+        const int64_t grid = resident_grid((B + 63) / 64, occupancy_per_cu(kernel, 256, 0, 2));
+        jf::launch(kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
     };
     switch ((N + 15) / 16) {
         case 1: go(mlp2_narrow_kernel<1>); break;

@@ -103,7 +103,7 @@ __global__ void __launch_bounds__(256, sizeof(T) == 8 ? 2 : 4) pair_gf_kernel(co
 
 template <typename T, int G> static int launch_pair_gf(const GfChainArgs<T>& a, const PairDims& pd, int64_t n_rows, size_t lds, T* tile, hipStream_t st) {
     auto k = pair_gf_kernel<T, G>;
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    allow_lds(k, lds);
     constexpr int R = 256 / G;
     const int64_t n_tiles = (pd.ni + R - 1) / R;
     jf::launch(k, dim3((unsigned)n_rows, pair_grid_y(n_rows, n_tiles)), dim3(256), lds, st, a, pd, tile);
@@ -209,7 +209,7 @@ __global__ void __launch_bounds__(256) pair_gfb_kernel(const GfChainArgs<T> a, c
 
 template <typename T, int D> static int launch_pair_gfb(const GfChainArgs<T>& a, const PairDims& pd, int64_t n_rows, size_t lds, T* tile, hipStream_t st) {
     auto k = pair_gfb_kernel<T, D>;
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    allow_lds(k, lds);
     const int64_t n_tiles = (pd.ni + 255) / 256;
     jf::launch(k, dim3((unsigned)n_rows, pair_grid_y(n_rows, n_tiles)), dim3(256), lds, st, a, pd, tile);
     return check_launch();
@@ -278,7 +278,7 @@ static int grid_gf(const T* x, int64_t xs, int64_t xgs, const T* params, int64_t
         max_k = a.L[l].K > max_k ? a.L[l].K : max_k;
     }
     const size_t lds_rows = ((size_t)a.tab_offset + (size_t)n_layers * max_k * D * 4) * sizeof(T);
-    if (classic && D <= 8 && lds_rows <= (size_t)160 * 1024) {
+    if (classic && D <= 8 && lds_rows <= JF_LDS_WG_MAX) {
         switch (D) {
             case 1: rc = launch_pair_gfb<T, 1>(a, pd, n_rows, lds_rows, tile, st); break;
             case 2: rc = launch_pair_gfb<T, 2>(a, pd, n_rows, lds_rows, tile, st); break;
@@ -455,10 +455,10 @@ static int grid_mchain(const T* x, int64_t xs, int64_t xgs, const T* params, int
         if (Fam::needs_tab(layers[l])) { const int w = fam_tab_words<Fam>::of(layers[l]); a.tab = w > a.tab ? w : a.tab; }
     a.shared_tab = (pair_has_build<Fam>::value && a.tab > 0) ? 1 : 0;
     const size_t lds = ((size_t)n_layers * a.tile_stride + (size_t)(a.shared_tab ? n_layers : 64) * a.tab + (size_t)64 * a.scratch) * sizeof(T);
-    if (lds > 160 * 1024) return JF_ERR_UNSUPPORTED;
+    if (lds > JF_LDS_WG_MAX) return JF_ERR_UNSUPPORTED;
     if (n_groups == 0 || pd.ni == 0) return JF_OK;
     auto k = pair_mchain_kernel<T, Fam>;
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    allow_lds(k, lds);
     const int64_t n_rows = n_groups * J, n_tiles = (pd.ni + 63) / 64;
     hipStream_t st = (hipStream_t)stream;
     jf::launch(k, dim3((unsigned)n_rows, pair_grid_y(n_rows, n_tiles)), dim3(64), lds, st, a, pd, tile);

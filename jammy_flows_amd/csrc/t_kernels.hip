@@ -272,19 +272,14 @@ static int t_layer_bwd(const T* x, int64_t xs, const T* params, int64_t ps, int3
     size_t lds = ((size_t)(a.P > 0 ? a.P : 1) * (a.bcast ? 1 : 64) + (a.bcast ? (size_t)a.P : 0)) * sizeof(T);
     // per-sample parameters: the tile is staged where it fits the LDS, else the lanes read their rows from global memory (same result, bit for bit).
     // JF_T_BWD_STAGE=0 (read at every call) takes the second kernel at every size: the check of that equality.
-    bool staged = a.bcast || lds <= 160 * 1024;
+    bool staged = a.bcast || lds <= JF_LDS_WG_MAX;
     if (!a.bcast) { const char* e = getenv("JF_T_BWD_STAGE"); if (e && atoi(e) == 0) staged = false; }
     if (!staged) lds = 0;
     auto k = staged ? (D <= 8 ? t_bwd_kernel<T, 8, true> : D <= 16 ? t_bwd_kernel<T, 16, true> : t_bwd_kernel<T, 32, true>)
                     : (D <= 8 ? t_bwd_kernel<T, 8, false> : D <= 16 ? t_bwd_kernel<T, 16, false> : t_bwd_kernel<T, 32, false>);
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    allow_lds(k, lds);
     int64_t grid = (B + 63) / 64;
-    if (a.bcast) {                                                 // a resident set of workgroups walks the tiles (eight per CU: the kernel is light)
-        int dev = 0, cus = 256;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (grid > (int64_t)cus * 8) grid = (int64_t)cus * 8;
-    }
+    if (a.bcast) grid = resident_grid(grid, 8);                    // a resident set of workgroups walks the tiles (eight per CU: the kernel is light)
     jf::launch(k, dim3((unsigned)grid), dim3(64), lds, (hipStream_t)stream, a);
     return check_launch();
 }

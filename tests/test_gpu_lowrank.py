@@ -198,6 +198,39 @@ def test_entry_points_directly_strided_inputs_and_argument_checks():
         _hip.lowrank_gf_chain_inv(t2.float(), u2, b2, x, None, larr, 2, 8)
 
 
+def test_dynamic_lds_opt_in_survives_a_larger_second_model(tmp_path):
+    """Two low-rank models in one process, the narrow / short one first: the kernels whose dynamic LDS grows with the hidden width
+    (jf_lowrank_head_bwd_f64) or the chain length (jf_lowrank_gf_chain_inv_f64) opt in above 48 KB once per device, and that once must cover the
+    larger model too.  tests/lowrank_lds_child.py derives the shapes and runs in fresh processes (nothing has set the attributes yet): the large
+    calls after the small ones return what they return in a process that makes only the large calls, bit for bit where the kernel has no
+    atomics; the head's backward (float64 LDS atomics) equals the per-stage sequence at the tolerance of
+    test_lowrank_head_equals_the_stage_sequence in both."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    res = {}
+    for mode in ("both", "large"):
+        path = str(tmp_path / (mode + ".npz"))
+        r = subprocess.run([sys.executable, os.path.join(root, "tests", "lowrank_lds_child.py"), mode, path], env=dict(os.environ, PYTHONPATH=root),
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
+        assert r.returncode == 0, (mode, r.returncode, r.stderr[-3000:])
+        res[mode] = dict(np.load(path))
+    both, large = res["both"], res["large"]
+    assert set(both) == set(large)
+    for k in both:                                             # the forward results of the entry points: no atomics, equal bit for bit
+        if ".g_" not in k and ".ref_" not in k:
+            assert np.array_equal(both[k], large[k]), k
+    assert bool(both["chain.supported"]) and np.isfinite(both["chain.z"]).all() and np.isfinite(both["chain.ld"]).all()
+    assert not bool(both["chain_max.supported"])               # JF_MAX_CHAIN layers need 189 KB: refused as unsupported, before and after
+    for r in (both, large):
+        for kt in (1, 2):
+            for n in ("out", "g_inp", "g_v1", "g_u1", "g_b1", "g_v2"):      # (that test bounds the weight gradients as one vector)
+                a, b = r["head%d.%s" % (kt, n)], r["head%d.ref_%s" % (kt, n)]
+                scale = np.abs(b).max() if n in ("out", "g_inp") else float(r["head%d.ref_par_absmax" % kt])
+                assert np.abs(a - b).max() <= 2e-12 * max(1.0, scale), (kt, n, np.abs(a - b).max())
+
+
 def test_differentiable_sampling_through_the_lowrank_chain():
     """pdf.sample(allow_gradients=True) on the C5 configuration: _differentiable_sample runs D + 1 backward passes through ONE graph that contains
     LowRankGfChainFn and LowRankHeadFn (retain_graph) -- the saved layer inputs must survive them; gradients equal the block sequence's"""
