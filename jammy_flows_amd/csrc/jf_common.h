@@ -283,11 +283,13 @@ template <typename T, int D> __device__ inline void store_d(T* __restrict__ p, c
 }
 
 // wave-aggregated status counter bump (one atomic per wave)
-__device__ inline void status_add(int32_t* status, int which, bool flag) {
+// (lane: the caller's index in its wave, for a kernel that does not want threadIdx.x kept in a register until its last line)
+__device__ inline void status_add(int32_t* status, int which, bool flag, unsigned lane) {
     if (status == nullptr) return;
     const unsigned long long m = __ballot(flag);
-    if (m != 0ull && (threadIdx.x & (JF_WAVE - 1)) == (unsigned)(__ffsll((long long)m) - 1)) atomicAdd(status + which, (int32_t)__popcll(m));
+    if (m != 0ull && lane == (unsigned)(__ffsll((long long)m) - 1)) atomicAdd(status + which, (int32_t)__popcll(m));
 }
+__device__ inline void status_add(int32_t* status, int which, bool flag) { status_add(status, which, flag, threadIdx.x & (JF_WAVE - 1)); }
 
 // launch status of the kernel just enqueued.  hipPeekAtLastError does not clear the sticky error state, so an error left behind by an
 // unrelated earlier call of the application is neither swallowed nor misattributed silently: it keeps surfacing until the caller handles it.

@@ -137,6 +137,30 @@ template <typename F> __device__ __forceinline__ void cs_rsum4(float a, float b,
     out[0] = t; out[1] = t1; out[2] = t2; out[3] = t3;
 }
 __device__ __forceinline__ float cs_rmax(float v) { return cs_rreduce(v, [](float a, float b) { return fmaxf(a, b); }); }
+// the row reductions of TWO values at once (one from each row group of a wave): X = reduction of x, Y = of y, in every lane.  Distinct
+// operands again, by 16-lane row: after permlane16_swap(x, y) x = {x0, y0, x2, y2} and y = {x1, y1, x3, y3}; s = op(x, y) =
+// {x01, y01, x23, y23}; after permlane32_swap(s, s) s = {x01, y01, x01, y01} and s2 = {x23, y23, x23, y23}; t = op(s, s2) = {X, Y, X, Y};
+// after permlane16_swap(t, t) t = {X, X, X, X} and t2 = {Y, Y, Y, Y}.  3 swaps, 2 ops and 2 copies where two cs_rreduce take 4, 4 and 4
+// (x and y are consumed: hand in temporaries and the first swap needs no copy); each result is combined in cs_rreduce's order (rows
+// 0 + 1, 2 + 3, then the two), so it carries the same bits
+template <typename Op> __device__ __forceinline__ void cs_rreduce2(float x, float y, Op op, float& X, float& Y) {
+    asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(x), "+v"(y));
+    float s = op(x, y), s2 = s;
+    asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(s), "+v"(s2));
+    float t = op(s, s2), t2 = t;
+    asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(t), "+v"(t2));
+    X = t; Y = t2;
+}
+__device__ __forceinline__ void cs_rsum2(float x, float y, float& X, float& Y) { cs_rreduce2(x, y, [](float a, float b) { return a + b; }, X, Y); }
+__device__ __forceinline__ void cs_rmax2(float x, float y, float& X, float& Y) { cs_rreduce2(x, y, [](float a, float b) { return fmaxf(a, b); }, X, Y); }
+
+// the lane's index in its wave, counted again by the hardware (lanes below this one): costs two instructions where it is wanted and no
+// register in between, where a value kept from threadIdx.x lives through the whole kernel.  volatile: it stays where it is written
+__device__ __forceinline__ int cs_lane_again() {
+    int l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return l;
+}
 
 static inline bool cs_layer_supported(const jf_gf_layer& h, int D) {
     return h.num_kde == CS_K && h.hh_iter >= 0 && h.hh_iter <= CS_HH && h.nonlinear_stretch_type == JF_GF_STRETCH_CLASSIC &&

@@ -49,6 +49,7 @@ __device__ __forceinline__ void cond_gf_split_body(const CsArgs& a, const int bl
     float* Xs = reinterpret_cast<float*>(smem_raw + G::CHUNK);   // phase 1 only (overlays buffer 1 while chunk 0 lands in buffer 0)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, lq = lane >> 4;
+    const int wave_s = __builtin_amdgcn_readfirstlane(wave);        // the wave's index in a scalar register (see the epilogue)
     const int64_t row0 = (int64_t)block * CS_ROWS;
     const int64_t last = a.B - 1;
     const int D = a.D;
@@ -59,12 +60,14 @@ __device__ __forceinline__ void cond_gf_split_body(const CsArgs& a, const int bl
     // of its 64-bit addresses, 230 per layer)
     const __amdgpu_buffer_rsrc_t packed_rsrc =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(a.packed), 0, a.n_layers * CS_CPL * G::CHUNK, 0x00027000);
-    const int lane_off = wave * 1024 + lane * 16;
+    // the wave's KiB piece is part of the scalar offset as well (wave_s), so the LDS address of every DMA instruction is scalar too: with the
+    // wave index taken from threadIdx.x it was a vector add and a v_readfirstlane per instruction, and two registers held through the kernel
+    const int lane_off = lane * 16;
     auto dma = [&](int chunk) {
         // the packed image is in the log-prob direction's consumption order (last layer first); the sampling direction walks the layers forwards
         const int img = FWD ? (a.n_layers - 1 - chunk / CS_CPL) * CS_CPL + chunk % CS_CPL : chunk;
-        const int g = img * G::CHUNK;
-        cs_dma_chunk(packed_rsrc, Ws0 + (chunk & 1) * G::CHUNK, g, lane_off, wave, lane, G::W, G::B);
+        const int g = img * G::CHUNK + wave_s * 1024;
+        cs_dma_chunk(packed_rsrc, Ws0 + (chunk & 1) * G::CHUNK, g, lane_off, wave_s, lane, G::W, G::B);
     };
     dma(0);                                                        // lands in buffer 0 while phase 1 works in buffer 1
 
@@ -72,7 +75,8 @@ __device__ __forceinline__ void cond_gf_split_body(const CsArgs& a, const int bl
     bf16x8 hB[RG][CS_KSTEPS][NP];
     cs_hidden<RG, false, NP>(a.in, a.in_stride, a.W1, a.w1s, a.b1, a.K1, a.H, row0, last, Xs, hB, nullptr, 0, a.cin.n ? &a.cin : nullptr);
     // ---- flow state: lane = (row li of the row group's 16, coordinate lq)
-    const bool live = lq < D, leader = lq == 0;
+    const bool live = lq < D;
+    bool leader = lq == 0;
     int d = live ? lq : D - 1;
     int64_t row[RG]; bool row_valid[RG];
     float x[RG], ld[RG];
@@ -167,27 +171,48 @@ __device__ __forceinline__ void cond_gf_split_body(const CsArgs& a, const int bl
         }
         // ---- flow phase on the lane's register rows (raw parameters; jf_gf.h arithmetic)
         const CsLayer o = a.L[l];                                  // uniform index: scalar loads from the kernarg segment
+        if constexpr (!FWD) {
+            // in stages over the wave's row groups, so that with RG = 2 the reductions over a row's four lanes carry one value of each
+            // row group (cs_rsum2: 3 swaps for two sums instead of 4, half as many serial chains); every sum keeps cs_rsum's order
+            auto rsum_groups = [](float (&v)[RG]) {
+                if constexpr (RG == 2) cs_rsum2(v[0], v[1], v[0], v[1]);
+                else
 #pragma unroll
-        for (int g = 0; g < RG; ++g) {
-            if constexpr (!FWD) {
-                float xg = fmaf(-P[g][CS_SLOT_OFF], pscale, x[g]);  // euclidean_base.py:40-45 (zero column when the layer models no offset)
-                // x <- Q^T x (gaussianization_flow.py:1038), H_i = I - 2 v v^T / |v|^2.  The four |v_i|^2 do not depend on x: one batched
-                // reduction, and 2 / |v_i|^2 taken once per row before the gather
-                // (a lane past the row's D coordinates holds v = 0: its columns of W2 and b2 are packed as zeros)
+                    for (int g = 0; g < RG; ++g) v[g] = cs_rsum(v[g]);
+            };
+            // x <- Q^T x (gaussianization_flow.py:1038), H_i = I - 2 v v^T / |v|^2.  The four |v_i|^2 do not depend on x: one batched
+            // reduction, and 2 / |v_i|^2 taken once per row before the gather
+            // (a lane past the row's D coordinates holds v = 0: its columns of W2 and b2 are packed as zeros)
+            float xg[RG], r2[RG][CS_HH];
+            // nothing of the flow phase is scheduled among the last chunk's MFMAs: with both row groups' norms and reflections ready to start
+            // there, the A fragments, the accumulators and eight r2 did not fit into 168 registers together (3 to 5 spilled without the barrier)
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int g = 0; g < RG; ++g) {
+                xg[g] = fmaf(-P[g][CS_SLOT_OFF], pscale, x[g]);    // euclidean_base.py:40-45 (zero column when the layer models no offset)
                 const float* v = &P[g][CS_SLOT_ROT];
-                float r2[CS_HH];
-                cs_rsum4(v[0] * v[0], v[1] * v[1], v[2] * v[2], v[3] * v[3], [](float n2) { return 2.0f * M<float>::rcp(n2); }, r2);
+                cs_rsum4(v[0] * v[0], v[1] * v[1], v[2] * v[2], v[3] * v[3], [](float n2) { return 2.0f * M<float>::rcp(n2); }, r2[g]);
+            }
 #pragma unroll
-                for (int i = 0; i < CS_HH; ++i) {
-                    if (i < o.hh) xg -= cs_rsum(v[i] * xg) * r2[i] * v[i];
+            for (int i = 0; i < CS_HH; ++i) {
+                if (i < o.hh) {
+                    float dot[RG];
+#pragma unroll
+                    for (int g = 0; g < RG; ++g) dot[g] = P[g][CS_SLOT_ROT + i] * xg[g];
+                    rsum_groups(dot);
+#pragma unroll
+                    for (int g = 0; g < RG; ++g) xg[g] -= dot[g] * r2[g][i] * P[g][CS_SLOT_ROT + i];
                 }
+            }
+            // the mixture one row group at a time: it holds the register peak
+            float logd[RG];
+#pragma unroll
+            for (int g = 0; g < RG; ++g) {
                 CsSums sums;
-                const MixQ<float> q = cs_mixture(P[g], o, pscale, xg, live, SAVE ? &sums : nullptr);
+                const MixQ<float> q = cs_mixture(P[g], o, pscale, xg[g], live, SAVE ? &sums : nullptr);
                 if constexpr (SAVE) {
                     {   // (row number re-derived from the lane index: see the epilogue)
-                        int t2 = tid;
-                        asm volatile("" : "+v"(t2));
-                        row[g] = row0 + ((t2 >> 6) * RG + g) * MT + (t2 & 15);
+                        row[g] = row0 + (wave_s * RG + g) * MT + (cs_lane_again() & 15);
                         row_valid[g] = row[g] <= last;
                     }
                     if (row_valid[g]) {
@@ -198,8 +223,14 @@ __device__ __forceinline__ void cond_gf_split_body(const CsArgs& a, const int bl
                 }
                 const IcdfOut<float> sy = gf_icdf<float>(o.inv_type, q);
                 x[g] = sy.y;
-                ld[g] += cs_rsum(live ? sy.logd : 0.f);
-            } else {
+                logd[g] = live ? sy.logd : 0.f;
+            }
+            rsum_groups(logd);
+#pragma unroll
+            for (int g = 0; g < RG; ++g) ld[g] += logd[g];
+        } else {
+#pragma unroll
+            for (int g = 0; g < RG; ++g) {
                 // sampling direction (gaussianization_flow.py:911-989): regulate the row once in its registers, solve stage(mixture(x)) = z by
                 // 25 bisection + <= 20 Newton steps, log-det from the solution, then x <- Q x and the offset (euclidean_base.py:63-68)
                 cs_derive(P[g], o);
@@ -224,17 +255,41 @@ __device__ __forceinline__ void cond_gf_split_body(const CsArgs& a, const int bl
     // The epilogue's row numbers are derived AGAIN from the lane index, behind an empty asm the compiler cannot see through: the copies made
     // before phase 1 (two 64-bit row numbers, the coordinate index) otherwise stay in registers through every layer, and at this kernel's 168
     // registers (three workgroups per CU) they were what spilled to scratch (8 registers: 36 B per lane written and read back, 75 MB per
-    // 2^20-row launch on the write counters).
+    // 2^20-row launch on the write counters).  The lane index itself comes from the hardware again (cs_lane_again) and the wave index from
+    // a scalar register, so that threadIdx.x is not held through the layers either; the status update takes the same lane index.
+    int lane2 = lane;
     if constexpr (!FWD) {                                          // (the sampling variants gain registers from it: 141 -> 153; they have none to spare either)
-        int t2 = tid;
-        asm volatile("" : "+v"(t2));
-        const int lane2 = t2 & 63, wave2 = t2 >> 6, li2 = lane2 & 15, lq2 = lane2 >> 4;
+        lane2 = cs_lane_again();
+        const int li2 = lane2 & 15, lq2 = lane2 >> 4;
         d = lq2 < D ? lq2 : D - 1;
+        leader = lq2 == 0;
 #pragma unroll
         for (int g = 0; g < RG; ++g) {
-            row[g] = row0 + (wave2 * RG + g) * MT + li2;
+            row[g] = row0 + (wave_s * RG + g) * MT + li2;
             row_valid[g] = row[g] <= last;
         }
+    }
+    // log-prob direction: the base log-prob sums and the non-finite flags of the wave's row groups, reduced together (cs_rreduce2)
+    float sb[RG], bad[RG];
+    if constexpr (!FWD) {
+#pragma unroll
+        for (int g = 0; g < RG; ++g) {
+            sb[g] = live ? -0.5f * x[g] * x[g] - M<float>::HALF_LN_2PI : 0.f;
+            bad[g] = (live && !M<float>::finite(x[g])) ? 1.f : 0.f;
+        }
+        if constexpr (RG == 2) {
+            if (a.blp_out) cs_rsum2(sb[0], sb[1], sb[0], sb[1]);
+            cs_rmax2(bad[0], bad[1], bad[0], bad[1]);
+        } else {
+#pragma unroll
+            for (int g = 0; g < RG; ++g) {
+                if (a.blp_out) sb[g] = cs_rsum(sb[g]);
+                bad[g] = cs_rmax(bad[g]);
+            }
+        }
+        if (!a.blp_out)
+#pragma unroll
+            for (int g = 0; g < RG; ++g) sb[g] = 0.f;
     }
 #pragma unroll
     for (int g = 0; g < RG; ++g) {
@@ -242,10 +297,8 @@ __device__ __forceinline__ void cond_gf_split_body(const CsArgs& a, const int bl
         if constexpr (FWD) {
             if (row_valid[g] && leader) a.ld_out[row[g]] = ld[g];
         } else {
-            float sb = 0.f;
-            if (a.blp_out) sb = cs_rsum(live ? -0.5f * x[g] * x[g] - M<float>::HALF_LN_2PI : 0.f);
             if (row_valid[g] && leader) {
-                float ldv = ld[g], bv = sb + (a.blp_in ? a.blp_in[row[g]] : 0.f);
+                float ldv = ld[g], bv = sb[g] + (a.blp_in ? a.blp_in[row[g]] : 0.f);
                 if (a.n_ld_pre > 0) {                               // uniform: list order, this block last (bit for bit jf_combine_rows)
                     float t = a.ld_pre[0][row[g]];
                     for (int i = 1; i < a.n_ld_pre; ++i) t += a.ld_pre[i][row[g]];
@@ -260,8 +313,7 @@ __device__ __forceinline__ void cond_gf_split_body(const CsArgs& a, const int bl
                 if (a.blp_out) a.blp_out[row[g]] = bv;
                 if (a.total) a.total[row[g]] = bv + ldv;
             }
-            const float bad = cs_rmax((live && !M<float>::finite(x[g])) ? 1.f : 0.f);
-            status_add(a.status, JF_STATUS_NONFINITE, row_valid[g] && leader && (bad > 0.f || !M<float>::finite(ld[g])));
+            status_add(a.status, JF_STATUS_NONFINITE, row_valid[g] && leader && (bad[g] > 0.f || !M<float>::finite(ld[g])), lane2);
         }
     }
 }

@@ -5,7 +5,8 @@
 
 Cross-compiles cond_split_kernels.hip with the Makefile's CXXFLAGS (device only, -S) -- or reads an assembly file made that way -- and
 reports for cond_gf_split_kernel<RG, FWD, SAVE, NP>: VGPRs, scratch, waves per SIMD allowed by the registers, and per region the count of
-vector instructions, transcendentals, MFMAs and s_nop with their weighted issue cycles.  Regions, in text order:
+vector instructions, transcendentals, MFMAs and s_nop with their weighted issue cycles, and of the row reductions' lane swaps
+(v_permlane16_swap / v_permlane32_swap).  Regions, in text order:
   phase1  everything in front of the layer loop (MLP input staging, tanh, f16 split) -- the layer loop is the one holding the MFMAs
   matrix  the layer loop's blocks up to its last MFMA (chunk DMA, LDS reads, MFMAs)
   flow    the rest of the layer loop (offset, reflections, mixture, inverse CDF, log-det reduction), every branch counted once
@@ -26,6 +27,7 @@ CSRC = os.path.join(ROOT, "jammy_flows_amd", "csrc")
 HIPCC = "/opt/rocm/bin/hipcc"
 TRANS = re.compile(r"^v_(exp|log|rcp|rsq|sqrt|sin|cos)_f(16|32)(_e32|_e64)?$")
 WEIGHT = {"trans": 8, "mfma": 8, "valu": 4, "nop": 4}
+SWAPS = {"swap16": "v_permlane16_swap", "swap32": "v_permlane32_swap"}       # the row reductions' lane exchanges (csrc/jf_cond_split.h)
 VGPR_POOL, VGPR_GRANULE, MAX_WAVES = 512, 8, 8
 
 
@@ -100,7 +102,7 @@ def budget(body):
     in_loop = [i for i, _ in ops if block_loop[i] == loop]
     first, last_loop = in_loop[0], in_loop[-1]
     last_mfma = max(i for i, op in ops if block_loop[i] == loop and classify(op) == "mfma")
-    regions = {r: {"valu": 0, "trans": 0, "mfma": 0, "nop": 0} for r in ("phase1", "matrix", "flow", "tail")}
+    regions = {r: {"valu": 0, "trans": 0, "mfma": 0, "nop": 0, "swap16": 0, "swap32": 0} for r in ("phase1", "matrix", "flow", "tail")}
     for i, op in ops:
         c = classify(op)
         if c is None:
@@ -110,6 +112,9 @@ def budget(body):
         else:
             r = "phase1" if i < first else ("tail" if i > last_loop else "phase1")
         regions[r][c] += 1
+        for k, name in SWAPS.items():                  # (counted as "valu" above; listed on their own as well)
+            if op.startswith(name):
+                regions[r][k] += 1
     for r in regions.values():
         r["vector"] = r["valu"] + r["trans"]          # non-MFMA vector instructions
         r["cycles"] = sum(WEIGHT[k] * r[k] for k in WEIGHT)
@@ -154,9 +159,9 @@ def main():
         return
     print("%s: %d VGPRs (+%d AGPRs), scratch %d B, spills v%d s%d, %d waves per SIMD by registers" %
           (r["kernel"], r["vgpr"], r["agpr"], r["scratch"], r["vgpr_spill"], r["sgpr_spill"], r["waves_per_simd"]))
-    print("%-7s %7s %7s %7s %7s %9s" % ("region", "vector", "trans", "mfma", "s_nop", "cycles"))
+    print("%-7s %7s %7s %7s %7s %9s %7s %7s" % ("region", "vector", "trans", "mfma", "s_nop", "cycles", "swap16", "swap32"))
     for k, v in r["regions"].items():
-        print("%-7s %7d %7d %7d %7d %9d" % (k, v["vector"], v["trans"], v["mfma"], v["nop"], v["cycles"]))
+        print("%-7s %7d %7d %7d %7d %9d %7d %7d" % (k, v["vector"], v["trans"], v["mfma"], v["nop"], v["cycles"], v["swap16"], v["swap32"]))
 
 
 if __name__ == "__main__":
