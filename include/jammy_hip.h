@@ -547,7 +547,17 @@ JF_DECLARE_MCHAIN(c, double, f64)
 /* A conditional manifold block in ONE launch: the default amortisation MLP params = tanh(in @ W1^T + b1) @ W2^T + b2
  * (main/default.py:656-670) followed by jf_<fam>_chain_inv (log-prob direction) or jf_<fam>_chain_fwd (sampling direction,
  * main/default.py:1482-1506: z = base points, no base log-prob) on those per-sample parameters.  The (B, N) block stays in LDS.
- * Limits: K1 <= 28, H <= 128, N = sum of the layers' row lengths <= 64, no correlated 'f'; otherwise JF_ERR_UNSUPPORTED. */
+ * Limits: K1 <= 28, H <= 128, N = sum of the layers' row lengths <= 64, no correlated 'f', and one workgroup's LDS (weights, parameter
+ * tiles, lane-private knot tables: it grows with K1, N and the largest bin count) within 160 KiB; otherwise JF_ERR_UNSUPPORTED, for every
+ * B including 0.  float32: the second product runs on f16 pairs under ONE power-of-two scale per W2, whatever the size of W2 (a scale
+ * exponent of either sign; entries below 2^-17 of the largest lose their low piece to the fixed f16 quantum 2^-24 under that scale).
+ * The layers behind it are float32 arithmetic.  Their tested range: with W2 drawn 0.5 N(0, 1) / sqrt(H) times 2 (parameters up to ~3)
+ * all four families meet the float64 reference at the bar of tests/cond_mchain_cases.py.  Times 4 (parameters up to ~5), the 'f' log-prob leaves it: kappa =
+ * exp(parameter) reaches 14, the von-Mises-Fisher step forms ret = 1 - 2 exp(-kappa (1 + cos theta)), which is 1 in float32 once the
+ * exponential is below 2^-24, and the chart then works on its clamp 1 - 1e-6 (csrc/jf_manifold.h:609-619; the generic form :421 loses
+ * the same; carrying log(1 - ret) instead of ret would not, and would no longer be the reference's formula).  Times 8 (up to ~10), 'r' leaves it too
+ * (a spline bin on its 1e-4 floor is the difference of two accumulated float32 knots: ~11 bits, csrc/jf_spline.h:100-101, :119-121) and
+ * 'f' rows turn non-finite -- counted in the status words.  The float64 entry points meet their bar at both. */
 #define JF_DECLARE_COND_MCHAIN(fam, T, suffix)                                                                                            \
     int jf_cond_##fam##_chain_inv_##suffix(const T* in, int64_t in_stride, const T* W1, int64_t w1_stride, const T* b1, const T* W2,        \
                                            int64_t w2_stride, const T* b2, int32_t K1, int32_t H, const T* x, int64_t x_stride,            \
@@ -592,7 +602,11 @@ JF_DECLARE_MCHAIN_BWD(c, float, f32)
 JF_DECLARE_MCHAIN_BWD(c, double, f64)
 
 /* intrinsic <-> embedding coordinates of S1 (angle <-> (cos, sin)) and S2 ((theta, phi) <-> (x, y, z)) with the log-det of
- * sphere_base.spherical_to_eucl_embedding / eucl_to_spherical_embedding (sphere_base.py:242-335); dim = 1 or 2 */
+ * sphere_base.spherical_to_eucl_embedding / eucl_to_spherical_embedding (sphere_base.py:242-335); dim = 1 or 2.
+ * Accuracy: towards the embedding a few u on every coordinate, a few u (1 + |log sin theta|) on the log-det, poles and seam included.
+ * The way back takes both angles from acos of a normalised coordinate, as the reference does (kept for value parity): the error of an
+ * angle a grows like u |cot a|, that of log sin(theta) like u cot^2(theta) -- at 1e-3 from a pole or from phi = 0 / pi about 400 u
+ * in the angle.  Within |cot a| <= 1 the angles are good to a few u (1 + |a|). */
 int jf_sphere_to_embedding_f32(const float* x, int64_t x_stride, const float* log_det_in, int64_t B, int32_t dim, float* x_out,
                                int64_t x_out_stride, float* log_det_out, void* stream);
 int jf_sphere_to_embedding_f64(const double* x, int64_t x_stride, const double* log_det_in, int64_t B, int32_t dim, double* x_out,

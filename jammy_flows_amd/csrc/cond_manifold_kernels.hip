@@ -44,7 +44,6 @@ static int cond_mchain(const T* in, int64_t in_stride, const T* W1, int64_t w1s,
         if constexpr (std::is_same<Fam, FFam>::value) { if (layers[l].correlated) return JF_ERR_UNSUPPORTED; }
     }
     if (col < 1 || col > CM_NMAX) return JF_ERR_UNSUPPORTED;
-    if (B == 0) return JF_OK;
     a.in = in; a.in_stride = in_stride; a.W1 = W1; a.w1s = w1s; a.b1 = b1; a.W2 = W2; a.w2s = w2s; a.b2 = b2; a.K1 = K1; a.H = H; a.N = col;
     a.x = x; a.xs = xs; a.ld_in = ld_in; a.B = B; a.n_layers = n_layers; a.dim = Fam::DIM;
     a.x_out = x_out; a.xos = xos; a.ld_out = ld_out; a.blp_in = blp_in; a.blp_out = blp_out; a.status = status;
@@ -64,7 +63,8 @@ static int cond_mchain(const T* in, int64_t in_stride, const T* W1, int64_t w1s,
     //  8 more elements behind the bias for the workgroup's absmax reduction)
     const size_t lds = ((size_t)CM_HMAX * ldk + CM_HMAX + (size_t)np * (CM_HMAX + 1) + np + 8 + (size_t)NT * ldk + (size_t)NT * a.tile_stride +
                         (size_t)NT * a.tab) * sizeof(T);
-    if (lds > JF_LDS_WG_MAX) return JF_ERR_UNSUPPORTED;
+    if (lds > JF_LDS_WG_MAX) return JF_ERR_UNSUPPORTED;      // the shape rules answer the same for every batch size, the empty one included
+    if (B == 0) return JF_OK;
     auto k = cond_mchain_kernel<T, Fam, NT, FWD>;
     allow_lds(k, lds);
     // one resident round of workgroups (occupancy x CUs, at most one per row tile)
