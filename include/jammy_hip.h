@@ -554,7 +554,7 @@ JF_DECLARE_MCHAIN(c, double, f64)
  * The layers behind it are float32 arithmetic.  Their tested range: with W2 drawn 0.5 N(0, 1) / sqrt(H) times 2 (parameters up to ~3)
  * all four families meet the float64 reference at the bar of tests/cond_mchain_cases.py.  Times 4 (parameters up to ~5), the 'f' log-prob leaves it: kappa =
  * exp(parameter) reaches 14, the von-Mises-Fisher step forms ret = 1 - 2 exp(-kappa (1 + cos theta)), which is 1 in float32 once the
- * exponential is below 2^-24, and the chart then works on its clamp 1 - 1e-6 (csrc/jf_manifold.h:609-619; the generic form :421 loses
+ * exponential is below 2^-24, and the chart then works on its clamp 1 - 1e-6 (csrc/jf_manifold.h:627-637; the generic form :439 loses
  * the same; carrying log(1 - ret) instead of ret would not, and would no longer be the reference's formula).  Times 8 (up to ~10), 'r' leaves it too
  * (a spline bin on its 1e-4 floor is the difference of two accumulated float32 knots: ~11 bits, csrc/jf_spline.h:100-101, :119-121) and
  * 'f' rows turn non-finite -- counted in the status words.  The float64 entry points meet their bar at both. */

@@ -12,6 +12,7 @@
 // matrix product's own rounding).  Exact-f32 MFMA issues at the VECTOR rate on CDNA4 and each of its operands was a scalar LDS read: the block
 // spent 0.06 of its 0.108 ms per 2^20 rows there.  W2 is cut into fragments by the workgroup itself (<= 64 x 128 values, L2-resident).
 #include "jf_cond_mchain.h"
+#include "jf_mchain_plan.h"
 #include "jf_merge.h"
 
 namespace jf {
@@ -31,32 +32,24 @@ template <typename T, class Fam, bool FWD = false>
 static int cond_mchain(const T* in, int64_t in_stride, const T* W1, int64_t w1s, const T* b1, const T* W2, int64_t w2s, const T* b2, int32_t K1, int32_t H,
                        const T* x, int64_t xs, const T* ld_in, int64_t B, int32_t n_layers, const typename Fam::CLayer* layers, T* x_out, int64_t xos,
                        T* ld_out, const T* blp_in, T* blp_out, int32_t* status, void* stream) {
-    if (!in || !W1 || !b1 || !W2 || !x || !x_out || !ld_out || !layers) return JF_ERR_BADARG;
-    if (!width_ok(K1) || !width_ok(H) || !rows_ok(B) || n_layers < 1 || n_layers > JF_MAX_MCHAIN) return JF_ERR_BADARG;
+    if (!in || !W1 || !b1 || !W2 || !x || !x_out || !ld_out) return JF_ERR_BADARG;
+    if (!width_ok(K1) || !width_ok(H) || !rows_ok(B)) return JF_ERR_BADARG;
     if (K1 > CM_K1MAX || H > CM_HMAX) return JF_ERR_UNSUPPORTED;
-    CmArgs<T, typename Fam::CLayer> a{};
-    int col = 0;
-    for (int l = 0; l < n_layers; ++l) {
-        if (!Fam::sane(layers[l])) return JF_ERR_BADARG;
-        a.L[l] = layers[l];
-        a.col0[l] = col;
-        col += Fam::row_len(layers[l]);
-        if constexpr (std::is_same<Fam, FFam>::value) { if (layers[l].correlated) return JF_ERR_UNSUPPORTED; }
-    }
+    ChainPlan<Fam> plan;
+    if (const int rc = plan_chain<Fam>(layers, n_layers, plan); rc != JF_OK) return rc;
+    if (plan.corr != 0) return JF_ERR_UNSUPPORTED;          // a correlated 'f' layer: the lanes of this kernel own no scratch for its MLP
+    const int col = plan.P;
     if (col < 1 || col > CM_NMAX) return JF_ERR_UNSUPPORTED;
+    CmArgs<T, typename Fam::CLayer> a{};
+    for (int l = 0; l < n_layers; ++l) { a.L[l] = layers[l]; a.col0[l] = plan.col0[l]; }
     a.in = in; a.in_stride = in_stride; a.W1 = W1; a.w1s = w1s; a.b1 = b1; a.W2 = W2; a.w2s = w2s; a.b2 = b2; a.K1 = K1; a.H = H; a.N = col;
     a.x = x; a.xs = xs; a.ld_in = ld_in; a.B = B; a.n_layers = n_layers; a.dim = Fam::DIM;
     a.x_out = x_out; a.xos = xos; a.ld_out = ld_out; a.blp_in = blp_in; a.blp_out = blp_out; a.status = status;
     const int np = (col + 15) / 16 * 16;
     a.tile_stride = np + 1;
     a.scratch = 0;
-    int n_spl = 0;
-    for (int l = 0; l < n_layers; ++l) n_spl += Fam::n_bins(layers[l]);
-    a.tab = 0;                                         // lane-private knot tables: none for a spline-free chain (default 'f', 'm'), else 3 (bins + 1)
-    if (n_spl > 0) {                                   // words where the family states its bin count (r, o), the 16-bin maximum otherwise
-        a.tab = 1;
-        for (int l = 0; l < n_layers; ++l) { const int w = fam_tab_words<Fam>::of(layers[l]); a.tab = w > a.tab ? w : a.tab; }
-    }
+    a.tab = plan.tab;                                  // lane-private knot tables: none for a spline-free chain (default 'f', 'm'), else 3 (bins + 1)
+                                                       // words of the chain's largest spline
     const int k1p = (K1 + 3) / 4 * 4, ldk = k1p + 1;
     constexpr int NT = sizeof(T) == 4 ? 256 : 128;
     // (float32: the W2 region holds np / 16 x 4 k-steps x 2 pieces x 1 KiB of f16 fragments = np x 128 floats, less than the np x 129 reserved;

@@ -48,12 +48,6 @@ template <typename T, int N> struct SeededRowN {
     __device__ __forceinline__ SeededRowN operator+(int k) const { return SeededRowN{p + k, seed0 - k}; }
 };
 
-template <typename T> __device__ __forceinline__ T gxr_wave_sum(T v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // where a lane's parameter gradients go: its own row of g_params (per-sample parameters), or -- wave sums -- the workgroup's row in LDS
 template <typename T> struct GradSink {
     T* row;            // per-sample: g_params + row * gps (nullptr for inactive lanes)
@@ -63,7 +57,7 @@ template <typename T> struct GradSink {
         if (!active) v = T(0);
         bad = bad || !M<T>::finite(v);
         if (acc) {
-            const T s = gxr_wave_sum<T>(v);
+            const T s = wave_sum<T>(v);
             if ((threadIdx.x & 63) == 0) atomicAdd(acc + col, s);
         } else if (active) {
             row[col] = v;

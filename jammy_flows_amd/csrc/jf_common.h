@@ -282,6 +282,13 @@ template <typename T, int D> __device__ inline void store_d(T* __restrict__ p, c
     }
 }
 
+// butterfly sum over the wave: every lane ends with the sum of all 64
+template <typename T> __device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
 // wave-aggregated status counter bump (one atomic per wave)
 // (lane: the caller's index in its wave, for a kernel that does not want threadIdx.x kept in a register until its last line)
 __device__ inline void status_add(int32_t* status, int which, bool flag, unsigned lane) {

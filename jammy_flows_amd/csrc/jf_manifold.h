@@ -45,10 +45,18 @@ __host__ inline bool sane_spline(const jf_spline_opts& s) {
     return s.num_bins >= 1 && s.num_bins <= JF_SPLINE_CAP && s.n_w >= 0 && s.n_w <= 4 * JF_SPLINE_CAP && s.n_h >= 0 &&
            s.n_h <= 4 * JF_SPLINE_CAP && s.n_d >= 0 && s.n_d <= 4 * JF_SPLINE_CAP;
 }
+// option limits (host): what the kernels implement of a spline's options -- the C2-smooth variant up to 3 bins.  Every family states its own
+// as Fam::supported; plan_chain (jf_mchain_plan.h) answers JF_ERR_UNSUPPORTED for a layer outside them, before it asks Fam::sane
+__host__ inline bool spline_supported(const jf_spline_opts& s) {
+    return s.num_bins >= 1 && s.num_bins <= JF_SPLINE_CAP && s.n_w >= 0 && s.n_h >= 0 && s.n_d >= 0 && (s.smooth == 0 || s.num_bins <= 3);
+}
 
 // per-lane knot-table elements a layer needs: the family's own count where it states one ('r', 'o', 'f': 3 (bins + 1)), else the fixed stride
 template <class Fam, class = void> struct fam_tab_words { static int of(const typename Fam::CLayer&) { return JF_SPLINE_TAB; } };
 template <class Fam> struct fam_tab_words<Fam, std::void_t<decltype(&Fam::tab_words)>> { static int of(const typename Fam::CLayer& L) { return Fam::tab_words(L); } };
+// families whose knot table does not depend on the row (Fam::HAS_BUILD + Fam::build): one table per workgroup where the parameters are shared
+template <class Fam, class = void> struct fam_has_build : std::false_type {};
+template <class Fam> struct fam_has_build<Fam, std::void_t<decltype(Fam::HAS_BUILD)>> : std::true_type {};
 
 // =================================================================================================  'r'
 template <typename T> __device__ __forceinline__ T r_core(const jf_r_layer& L, const T* __restrict__ p, T x, T& ld, LaneCtx<T>& c, bool inverse) {
@@ -69,6 +77,7 @@ struct RFam {
     template <typename T> static __device__ __forceinline__ void build(const CLayer& L, const T* __restrict__ p, T* __restrict__ tab) {
         spline_interval_build<T>(p, to_dev<T>(L.sp), tab, (T)L.lo, (T)L.hi);
     }
+    static __host__ bool supported(const CLayer& L) { return spline_supported(L.sp); }
     static __host__ bool sane(const CLayer& L) { return sane_spline(L.sp); }
     static __host__ int row_len(const CLayer& L) { return spline_row_len(L.sp); }
     static __host__ int n_bins(const CLayer&) { return 1; }
@@ -118,6 +127,7 @@ template <typename T> __device__ __forceinline__ T o_core(const jf_o_layer& L, c
 struct OFam {
     using CLayer = jf_o_layer;
     static constexpr int DIM = 1;
+    static __host__ bool supported(const CLayer& L) { return spline_supported(L.sp); }
     static __host__ bool sane(const CLayer& L) { return sane_spline(L.sp) && sane_hh(L.hh_iter); }
     static __host__ int row_len(const CLayer& L) { return rot_len(L.hh_iter, 2) + spline_row_len(L.sp); }
     static __host__ int n_bins(const CLayer&) { return 1; }
@@ -232,6 +242,7 @@ struct MFam {
     using CLayer = jf_m_layer;
     static constexpr int DIM = 1;
     static __host__ __device__ int omega_pars(const CLayer& L) { return L.omega_pars == 3 ? 3 : 4; }
+    static __host__ bool supported(const CLayer&) { return true; }
     static __host__ bool sane(const CLayer& L) { return L.num_components >= 1 && L.num_components <= 4096 && sane_hh(L.hh_iter); }
     static __host__ int row_len(const CLayer& L) { return rot_len(L.hh_iter, 2) + omega_pars(L) * L.num_components; }
     static __host__ int n_bins(const CLayer&) { return 0; }
@@ -270,6 +281,7 @@ struct MFam {
 struct CFam {
     using CLayer = jf_c_layer;
     static constexpr int DIM = 2;      // interval / S1 use column 0 only (the host passes dim)
+    static __host__ bool supported(const CLayer&) { return true; }      // (a kind outside 0..2 is no option beyond the kernels but a bad argument: sane)
     static __host__ bool sane(const CLayer& L) { return L.kind >= 0 && L.kind <= 2 && sane_hh(L.hh_iter); }
     static __host__ int row_len(const CLayer& L) { return rot_len(L.hh_iter, L.kind == 2 ? 3 : 2); }
     static __host__ int n_bins(const CLayer&) { return 0; }
@@ -348,6 +360,12 @@ struct FFam {
             case JF_F_KAPPA_QUATVEC: return M<T>::sqrt(rot[1] * rot[1] + rot[2] * rot[2] + rot[3] * rot[3]);
             default: return rot[1] * rot[1] + rot[2] * rot[2] + rot[3] * rot[3];
         }
+    }
+    static __host__ bool supported(const CLayer& L) {                   // (the nested counts first: they bound the two loops)
+        if (L.n_vertical < 0 || L.n_vertical > JF_MAX_NESTED || L.n_circular < 0 || L.n_circular > JF_MAX_NESTED) return false;
+        for (int i = 0; i < L.n_vertical; ++i) if (!spline_supported(L.vertical[i].sp)) return false;
+        for (int i = 0; i < L.n_circular; ++i) if (!spline_supported(L.circular[i].sp)) return false;
+        return true;
     }
     static __host__ bool sane(const CLayer& L) {
         if (!sane_hh(L.hh_iter) || L.n_vertical < 0 || L.n_vertical > JF_MAX_NESTED || L.n_circular < 0 || L.n_circular > JF_MAX_NESTED) return false;

@@ -15,9 +15,8 @@
 #include <type_traits>
 
 #include "jf_dual.h"
-#include "jf_expmap.h"
-#include "jf_manifold.h"
 #include "jf_manifold_rev.h"
+#include "jf_mchain_plan.h"       // (jf_manifold.h, jf_expmap.h)
 #include "jf_spline_adj.h"
 
 namespace jf {
@@ -44,15 +43,6 @@ __device__ __forceinline__ int VFam_row_len_dev(const jf_v_layer& L) {
     const int n_pot = L.exp_map_type == JF_V_SPLINES ? 4 + 3 * JF_V_SPLINE_BINS + 1 : 3 + (L.exp_map_type == JF_V_EXPONENTIAL ? 2 : 1);
     return rot_len(L.hh_iter, 3) + n_pot * L.num_components;
 }
-
-template <typename T> __device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-template <class Fam, class = void> struct bwd_has_build : std::false_type {};
-template <class Fam> struct bwd_has_build<Fam, std::void_t<decltype(Fam::HAS_BUILD)>> : std::true_type {};
 
 // Broadcast parameters of a family whose knot table does not depend on the row ('r'): a pass's dual tables are the same for EVERY row, and
 // building them (softmax + cumulative sums + softplus on N-tangent duals: ~3 bins transcendentals per layer) is most of a pass.  The resident
@@ -144,7 +134,7 @@ template <typename T, class Fam, int N>
 __global__ void __launch_bounds__(64) mchain_bwd_kernel(const MBwdArgs<T, typename Fam::CLayer> a) {
     using Du = DualN<T, N>;
     extern __shared__ __align__(16) unsigned char smem_raw[];
-    if constexpr (bwd_has_build<Fam>::value) {
+    if constexpr (fam_has_build<Fam>::value) {
         if (a.shared_tab) { mchain_bwd_shared_tab<T, Fam, N>(a, smem_raw); return; }      // (uniform)
     }
     Du* tile = reinterpret_cast<Du*>(smem_raw);
@@ -922,32 +912,19 @@ template <typename T, class Fam>
 static int mchain_bwd(const T* x, int64_t xs, const T* params, int64_t ps, int32_t pb, int64_t B, int32_t n_layers, const typename Fam::CLayer* layers,
                       const T* g_xout, int64_t gxos, const T* g_ld, const T* g_blp, T* g_x, int64_t gxs, T* g_params, int64_t gps, int32_t* status,
                       void* stream) {
-    if (!x || !g_x || !layers || n_layers < 1 || n_layers > JF_MAX_MCHAIN || B < 0) return JF_ERR_BADARG;
+    if (!x || !g_x || B < 0) return JF_ERR_BADARG;
     if (pb != 1 && pb != B) return JF_ERR_BADARG;
+    ChainPlan<Fam> plan;
+    if (const int rc = plan_chain<Fam>(layers, n_layers, plan); rc != JF_OK) return rc;
+    if (plan.P > 0 && (!params || !g_params)) return JF_ERR_BADARG;
     if (B == 0) return JF_OK;
     MBwdArgs<T, typename Fam::CLayer> a{};
-    int col = 0;
-    for (int l = 0; l < n_layers; ++l) {
-        if (!Fam::sane(layers[l])) return JF_ERR_BADARG;
-        a.L[l] = layers[l];
-        a.col0[l] = col;
-        col += Fam::row_len(layers[l]);
-    }
-    if (col > 0 && (!params || !g_params)) return JF_ERR_BADARG;
-    a.x = x; a.xs = xs; a.params = params; a.ps = ps; a.bcast = (pb == 1) ? 1 : 0; a.B = B; a.n_layers = n_layers; a.P = col;
-    a.tile_stride = col > 0 ? col : 1;
-    a.dim = Fam::DIM;
-    if constexpr (std::is_same<Fam, CFam>::value) a.dim = layers[0].kind == 2 ? 2 : 1;
+    for (int l = 0; l < n_layers; ++l) { a.L[l] = layers[l]; a.col0[l] = plan.col0[l]; }
+    a.x = x; a.xs = xs; a.params = params; a.ps = ps; a.bcast = (pb == 1) ? 1 : 0; a.B = B; a.n_layers = n_layers; a.P = plan.P;
+    a.tile_stride = plan.P > 0 ? plan.P : 1;
+    a.dim = plan.dim;
     a.g_xout = g_xout; a.gxos = gxos; a.g_ld = g_ld; a.g_blp = g_blp; a.g_x = g_x; a.gxs = gxs; a.g_params = g_params; a.gps = gps; a.status = status;
-    a.scratch = 0;
-    if constexpr (std::is_same<Fam, FFam>::value) {
-        for (int l = 0; l < n_layers; ++l) {
-            if (!layers[l].correlated) continue;
-            if (layers[l].corr_hidden < 1 || layers[l].corr_rank < 0 || FFam::corr_out(layers[l]) + layers[l].corr_rank > JF_CORR_SCRATCH - 1)
-                return JF_ERR_UNSUPPORTED;
-            a.scratch = JF_CORR_SCRATCH;
-        }
-    }
+    a.scratch = plan.corr;
     bool staged = false;
     constexpr int lv = 1;                                          // staged 'v' kernel: lanes per row (the kernel is written for 1, 4, 8; see its header)
     if constexpr (std::is_same<Fam, VFam>::value) {               // all layers in the default direction: the staged kernel
@@ -964,20 +941,15 @@ static int mchain_bwd(const T* x, int64_t xs, const T* params, int64_t ps, int32
             for (int l = 0; l < n_layers; ++l) a.rot_max = rot_len(layers[l].hh_iter, 3) > a.rot_max ? rot_len(layers[l].hh_iter, 3) : a.rot_max;
         }
     }
-    a.tab = 0;
-    for (int l = 0; l < n_layers; ++l) {
-        if (!Fam::needs_tab(layers[l])) continue;
-        const int w = fam_tab_words<Fam>::of(layers[l]);           // families that state their bin count ('r', 'o', 'f'): 3 (bins + 1) words per lane, as in
+    a.tab = plan.tab;                                              // families that state their bin count ('r', 'o', 'f'): 3 (bins + 1) words per lane, as in
                                                                    // the forward kernels (35 for 10 bins, not 53)
-        a.tab = w > a.tab ? w : a.tab;
-    }
     a.rows = 64 / lv;
     size_t lds = 0;
     // generic kernel: four directions per pass when a full wave of rows still fits the LDS with the wider dual rows, else one
     constexpr int NW = std::is_same<Fam, FFam>::value && sizeof(T) == 4 ? 6 : 4;    // 'f' float32 (2 + 10 directions by default): two passes
     bool wide = false;
     if (!staged) {
-        a.shared_tab = (bwd_has_build<Fam>::value && a.bcast && a.tab > 0) ? 1 : 0;      // ('r' with permanent parameters: mchain_bwd_shared_tab)
+        a.shared_tab = (fam_has_build<Fam>::value && a.bcast && a.tab > 0) ? 1 : 0;      // ('r' with permanent parameters: mchain_bwd_shared_tab)
         const size_t lds4 = ((size_t)(a.bcast ? 1 : 64) * a.tile_stride + (size_t)(a.shared_tab ? n_layers : 64) * a.tab + (size_t)64 * a.scratch) * sizeof(DualN<T, NW>) +
                             (a.bcast ? (size_t)a.P * sizeof(T) : 0);
         wide = lds4 <= 64 * 1024;                                  // (also leaves room for two workgroups per CU)

@@ -6,8 +6,7 @@
 // A second LDS region holds the lane-private spline knot tables (jf_spline.h).
 #include <type_traits>
 
-#include "jf_expmap.h"
-#include "jf_manifold.h"
+#include "jf_mchain_plan.h"
 
 namespace jf {
 
@@ -42,9 +41,7 @@ template <typename T, typename CLayer> struct MChainArgs {
     T* total;
 };
 
-// (fam_tab_words: jf_manifold.h)
-template <class Fam, class = void> struct fam_has_build : std::false_type {};
-template <class Fam> struct fam_has_build<Fam, std::void_t<decltype(Fam::HAS_BUILD)>> : std::true_type {};
+// (fam_tab_words, fam_has_build: jf_manifold.h)
 
 template <typename T, class Fam, bool FWD>
 __global__ void __launch_bounds__(64) mchain_kernel(const MChainArgs<T, typename Fam::CLayer> a) {
@@ -131,45 +128,32 @@ static int mchain(const T* x, int64_t xs, const T* ld_in, const T* params, int64
                   const typename Fam::CLayer* layers, T* x_out, int64_t xos, T* ld_out, const T* blp_in, T* blp_out, int64_t* bins,
                   int64_t bins_stride, int32_t* status, void* stream, const jf_row_list* ld_pre = nullptr, const jf_row_list* blp_pre = nullptr,
                   T* total = nullptr) {
-    if (!x || !x_out || !ld_out || !layers || n_layers < 1 || n_layers > JF_MAX_MCHAIN || B < 0) return JF_ERR_BADARG;
+    if (!x || !x_out || !ld_out || B < 0) return JF_ERR_BADARG;
     if ((ld_pre || blp_pre || total) && (FWD || !blp_out)) return JF_ERR_BADARG;
     if ((ld_pre && (ld_pre->n < 0 || ld_pre->n > MC_MAX_PRE)) || (blp_pre && (blp_pre->n < 0 || blp_pre->n > MC_MAX_PRE))) return JF_ERR_UNSUPPORTED;
     if (ld_pre) for (int i = 0; i < ld_pre->n; ++i) if (!ld_pre->p[i]) return JF_ERR_BADARG;
     if (blp_pre) for (int i = 0; i < blp_pre->n; ++i) if (!blp_pre->p[i]) return JF_ERR_BADARG;
     if (pb != 1 && pb != B) return JF_ERR_BADARG;
+    ChainPlan<Fam> plan;
+    if (const int rc = plan_chain<Fam>(layers, n_layers, plan); rc != JF_OK) return rc;
+    if (plan.P > 0 && !params) return JF_ERR_BADARG;
     if (B == 0) return JF_OK;
     MChainArgs<T, typename Fam::CLayer> a{};
     a.x = x; a.xs = xs; a.ld_in = ld_in; a.params = params; a.ps = ps; a.bcast = (pb == 1) ? 1 : 0; a.B = B; a.n_layers = n_layers;
-    int col = 0, maxp = 0;
     for (int l = 0; l < n_layers; ++l) {
-        if (!Fam::sane(layers[l])) return JF_ERR_BADARG;
         a.L[l] = layers[l];
-        const int n = Fam::row_len(layers[l]);
-        a.col0[l] = col; a.ncols[l] = n;
-        a.vec_ok[l] = (!a.bcast && n > 0 && aligned16<T>(params, ps, col) && (n % Vec16<T>::N == 0)) ? 1 : 0;
-        col += n;
-        if (n > maxp) maxp = n;
+        const int n = plan.ncols[l];
+        a.col0[l] = plan.col0[l]; a.ncols[l] = n;
+        a.vec_ok[l] = (!a.bcast && n > 0 && aligned16<T>(params, ps, plan.col0[l]) && (n % Vec16<T>::N == 0)) ? 1 : 0;
     }
-    if (col > 0 && !params) return JF_ERR_BADARG;
-    a.tile_stride = padded_stride<T>(maxp > 0 ? maxp : 1);
-    a.dim = Fam::DIM;
-    if constexpr (std::is_same<Fam, CFam>::value) a.dim = layers[0].kind == 2 ? 2 : 1;
+    a.tile_stride = padded_stride<T>(plan.max_row > 0 ? plan.max_row : 1);
+    a.dim = plan.dim;
     a.x_out = x_out; a.xos = xos; a.ld_out = ld_out; a.blp_in = blp_in; a.blp_out = blp_out; a.bins = bins; a.bins_stride = bins_stride; a.status = status;
     if (ld_pre) { for (int i = 0; i < ld_pre->n; ++i) a.ld_pre[i] = static_cast<const T*>(ld_pre->p[i]); a.n_ld_pre = ld_pre->n; }
     if (blp_pre) { for (int i = 0; i < blp_pre->n; ++i) a.blp_pre[i] = static_cast<const T*>(blp_pre->p[i]); a.n_blp_pre = blp_pre->n; }
     a.total = total;
-    a.scratch = 0;
-    if constexpr (std::is_same<Fam, FFam>::value) {
-        for (int l = 0; l < n_layers; ++l) {
-            if (!layers[l].correlated) continue;
-            if (layers[l].corr_hidden < 1 || layers[l].corr_rank < 0 || FFam::corr_out(layers[l]) + layers[l].corr_rank > JF_CORR_SCRATCH - 1)
-                return JF_ERR_UNSUPPORTED;
-            a.scratch = JF_CORR_SCRATCH;
-        }
-    }
-    a.tab = 0;
-    for (int l = 0; l < n_layers; ++l)
-        if (Fam::needs_tab(layers[l])) { const int w = fam_tab_words<Fam>::of(layers[l]); a.tab = w > a.tab ? w : a.tab; }
+    a.scratch = plan.corr;
+    a.tab = plan.tab;
     a.rows = 64;
     a.shared_tab = (fam_has_build<Fam>::value && a.bcast && a.tab > 0) ? 1 : 0;
     size_t lds = 0;
@@ -183,10 +167,6 @@ static int mchain(const T* x, int64_t xs, const T* ld_in, const T* params, int64
     allow_lds(k, lds);
     jf::launch(k, dim3((unsigned)((B + a.rows - 1) / a.rows)), dim3(64), lds, (hipStream_t)stream, a);
     return check_launch();
-}
-
-static bool spline_ok(const jf_spline_opts& s) {
-    return s.num_bins >= 1 && s.num_bins <= JF_SPLINE_CAP && s.n_w >= 0 && s.n_h >= 0 && s.n_d >= 0 && (s.smooth == 0 || s.num_bins <= 3);
 }
 
 // ---- sphere <-> embedding
@@ -221,50 +201,35 @@ static int embed(const T* x, int64_t xs, const T* ld_in, int64_t B, int32_t dim,
 
 using namespace jf;
 
-#define JF_DEFINE_MCHAIN(fam, Fam, T, suffix, CHECK)                                                                                           \
+#define JF_DEFINE_MCHAIN(fam, Fam, T, suffix)                                                                                                  \
     extern "C" int jf_##fam##_chain_inv_##suffix(const T* x, int64_t xs, const T* ld_in, const T* p, int64_t ps, int32_t pb, int64_t B, int32_t n, \
                                                  const jf_##fam##_layer* L, T* xo, int64_t xos, T* ldo, const T* bi, T* bo, int64_t* bins,     \
                                                  int64_t bst, int32_t* st, void* s) {                                                          \
-        CHECK                                                                                                                                  \
         return mchain<T, Fam, false>(x, xs, ld_in, p, ps, pb, B, n, L, xo, xos, ldo, bi, bo, bins, bst, st, s);                                \
     }                                                                                                                                          \
     extern "C" int jf_##fam##_chain_inv_sum_##suffix(const T* x, int64_t xs, const T* ld_in, const T* p, int64_t ps, int32_t pb, int64_t B,     \
                                                      int32_t n, const jf_##fam##_layer* L, T* xo, int64_t xos, T* ldo, const T* bi, T* bo,      \
                                                      const jf_row_list* ldp, const jf_row_list* blpp, T* tot, int64_t* bins, int64_t bst,       \
                                                      int32_t* st, void* s) {                                                                    \
-        CHECK                                                                                                                                  \
         return mchain<T, Fam, false>(x, xs, ld_in, p, ps, pb, B, n, L, xo, xos, ldo, bi, bo, bins, bst, st, s, ldp, blpp, tot);                \
     }                                                                                                                                          \
     extern "C" int jf_##fam##_chain_fwd_##suffix(const T* x, int64_t xs, const T* ld_in, const T* p, int64_t ps, int32_t pb, int64_t B, int32_t n, \
                                                  const jf_##fam##_layer* L, T* xo, int64_t xos, T* ldo, const T* bi, T* bo, int64_t* bins,     \
                                                  int64_t bst, int32_t* st, void* s) {                                                          \
-        CHECK                                                                                                                                  \
         return mchain<T, Fam, true>(x, xs, ld_in, p, ps, pb, B, n, L, xo, xos, ldo, bi, bo, bins, bst, st, s);                                 \
     }
 
-#define CHECK_R if (L) for (int i = 0; i < n && i < JF_MAX_MCHAIN; ++i) if (!spline_ok(L[i].sp)) return JF_ERR_UNSUPPORTED;
-#define CHECK_O CHECK_R
-#define CHECK_M
-#define CHECK_F                                                                                          \
-    if (L) for (int i = 0; i < n && i < JF_MAX_MCHAIN; ++i) {                                                \
-        if (L[i].n_vertical < 0 || L[i].n_vertical > JF_MAX_NESTED || L[i].n_circular < 0 || L[i].n_circular > JF_MAX_NESTED) return JF_ERR_UNSUPPORTED; \
-        for (int j = 0; j < L[i].n_vertical; ++j) if (!spline_ok(L[i].vertical[j].sp)) return JF_ERR_UNSUPPORTED;   \
-        for (int j = 0; j < L[i].n_circular; ++j) if (!spline_ok(L[i].circular[j].sp)) return JF_ERR_UNSUPPORTED;   \
-    }
-#define CHECK_V if (L) for (int i = 0; i < n && i < JF_MAX_MCHAIN; ++i) if (L[i].exp_map_type < 0 || L[i].exp_map_type > JF_V_SPLINES) return JF_ERR_UNSUPPORTED;
-
-JF_DEFINE_MCHAIN(r, RFam, float, f32, CHECK_R)
-JF_DEFINE_MCHAIN(r, RFam, double, f64, CHECK_R)
-JF_DEFINE_MCHAIN(o, OFam, float, f32, CHECK_O)
-JF_DEFINE_MCHAIN(o, OFam, double, f64, CHECK_O)
-JF_DEFINE_MCHAIN(m, MFam, float, f32, CHECK_M)
-JF_DEFINE_MCHAIN(m, MFam, double, f64, CHECK_M)
-JF_DEFINE_MCHAIN(f, FFam, float, f32, CHECK_F)
-JF_DEFINE_MCHAIN(f, FFam, double, f64, CHECK_F)
-JF_DEFINE_MCHAIN(v, VFam, double, f64, CHECK_V)
-#define CHECK_C if (L) for (int i = 0; i < n && i < JF_MAX_MCHAIN; ++i) if (L[i].kind < 0 || L[i].kind > 2 || L[i].kind != L[0].kind) return JF_ERR_BADARG;
-JF_DEFINE_MCHAIN(c, CFam, float, f32, CHECK_C)
-JF_DEFINE_MCHAIN(c, CFam, double, f64, CHECK_C)
+JF_DEFINE_MCHAIN(r, RFam, float, f32)
+JF_DEFINE_MCHAIN(r, RFam, double, f64)
+JF_DEFINE_MCHAIN(o, OFam, float, f32)
+JF_DEFINE_MCHAIN(o, OFam, double, f64)
+JF_DEFINE_MCHAIN(m, MFam, float, f32)
+JF_DEFINE_MCHAIN(m, MFam, double, f64)
+JF_DEFINE_MCHAIN(f, FFam, float, f32)
+JF_DEFINE_MCHAIN(f, FFam, double, f64)
+JF_DEFINE_MCHAIN(v, VFam, double, f64)
+JF_DEFINE_MCHAIN(c, CFam, float, f32)
+JF_DEFINE_MCHAIN(c, CFam, double, f64)
 
 // the reference asserts float64 for 'v' (exponential_map_s2.py:450, 493): there is no float32 oracle, hence no float32 kernel
 extern "C" int jf_v_chain_inv_f32(const float*, int64_t, const float*, const float*, int64_t, int32_t, int64_t, int32_t, const jf_v_layer*, float*, int64_t,

@@ -15,6 +15,7 @@
 
 #include "jf_manifold_adj.h"
 #include "jf_manifold_rev.h"
+#include "jf_mchain_plan.h"
 
 namespace jf {
 
@@ -34,12 +35,6 @@ template <typename T, typename CLayer> struct MRevArgs {
     T* g_params; int64_t gps;
     int32_t* status;
 };
-
-template <typename T> __device__ __forceinline__ T rev_wave_sum(T v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 constexpr int REV_XIN = 2 * JF_MAX_MCHAIN;                      // per lane: every layer's input (<= 2 coordinates)
 
@@ -238,7 +233,7 @@ __global__ void __launch_bounds__(64) mchain_rev_kernel(const MRevArgs<T, typena
             for (int j = 0; j < a.P; ++j) {
                 const T v = active ? grow[j] : T(0);
                 bad = bad || !M<T>::finite(v);
-                const T s = rev_wave_sum<T>(v);
+                const T s = wave_sum<T>(v);
                 if (tid == 0) accp[j] += s;
             }
         } else {
@@ -267,17 +262,18 @@ template <typename T, class Fam, class Adj>
 static int mchain_rev(const T* x, int64_t xs, const T* params, int64_t ps, int32_t pb, int64_t B, int32_t n_layers, const typename Fam::CLayer* layers,
                       const T* g_xout, int64_t gxos, const T* g_ld, const T* g_blp, T* g_x, int64_t gxs, T* g_params, int64_t gps, int32_t* status,
                       void* stream) {
-    if (!x || !g_x || !layers || n_layers < 1 || n_layers > JF_MAX_MCHAIN || B < 0) return JF_ERR_BADARG;
+    if (!x || !g_x || B < 0) return JF_ERR_BADARG;
     if (pb != 1 && pb != B) return JF_ERR_BADARG;
+    ChainPlan<Fam> plan;
+    if (const int rc = plan_chain<Fam>(layers, n_layers, plan); rc != JF_OK) return rc;
+    const int col = plan.P;
+    if (col > 0 && (!params || !g_params)) return JF_ERR_BADARG;
     if (B == 0) return JF_OK;
     MRevArgs<T, typename Fam::CLayer> a{};
-    int col = 0;
     bool all_hand = true;
     for (int l = 0; l < n_layers; ++l) {
-        if (!Fam::sane(layers[l])) return JF_ERR_BADARG;
         a.L[l] = layers[l];
-        a.col0[l] = col;
-        col += Fam::row_len(layers[l]);
+        a.col0[l] = plan.col0[l];
         const int s = Adj::scr_words(layers[l]), c = Adj::corr_words(layers[l]), dr = Adj::dual_row(layers[l]), dt = Adj::dual_tab(layers[l]);
         a.scr = s > a.scr ? s : a.scr;
         a.corr = c > a.corr ? c : a.corr;
@@ -285,17 +281,7 @@ static int mchain_rev(const T* x, int64_t xs, const T* params, int64_t ps, int32
         a.dtab = dt > a.dtab ? dt : a.dtab;
         all_hand = all_hand && dr == 0 && dt == 0;
     }
-    if (col > 0 && (!params || !g_params)) return JF_ERR_BADARG;
-    if constexpr (std::is_same<Fam, FFam>::value) {
-        for (int l = 0; l < n_layers; ++l) {
-            if (!layers[l].correlated) continue;
-            if (layers[l].corr_hidden < 1 || layers[l].corr_rank < 0 || FFam::corr_out(layers[l]) + layers[l].corr_rank > JF_CORR_SCRATCH - 1)
-                return JF_ERR_UNSUPPORTED;
-        }
-    }
-    // the forward sweep's knot tables live in the same scratch
-    for (int l = 0; l < n_layers; ++l)
-        if (Fam::needs_tab(layers[l])) { const int w = fam_tab_words<Fam>::of(layers[l]); a.scr = w > a.scr ? w : a.scr; }
+    a.scr = plan.tab > a.scr ? plan.tab : a.scr;                   // the forward sweep's knot tables live in the same scratch
     if ((a.scr + a.corr) % 2 == 0) a.scr += 1;                     // odd lane stride (REV_XIN is even)
     a.x = x; a.xs = xs; a.params = params; a.ps = ps; a.bcast = (pb == 1) ? 1 : 0; a.B = B; a.n_layers = n_layers; a.P = col;
     a.tile_stride = col > 0 ? (col | 1) : 1;

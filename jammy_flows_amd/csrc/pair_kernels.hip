@@ -20,8 +20,7 @@
 #include <type_traits>
 
 #include "jf_gfb.h"
-#include "jf_expmap.h"
-#include "jf_manifold.h"
+#include "jf_mchain_plan.h"
 
 namespace jf {
 
@@ -333,15 +332,12 @@ template <typename T, typename CLayer> struct MPairArgs {
     int32_t* status;
 };
 
-template <class Fam, class = void> struct pair_has_build : std::false_type {};
-template <class Fam> struct pair_has_build<Fam, std::void_t<decltype(Fam::HAS_BUILD)>> : std::true_type {};
-
 template <typename T, class Fam>
 __global__ void __launch_bounds__(64) pair_mchain_kernel(const MPairArgs<T, typename Fam::CLayer> a, const PairDims pd, T* __restrict__ tile_out) {
     extern __shared__ __align__(16) unsigned char smem_raw[];
     T* rows = reinterpret_cast<T*>(smem_raw);
     const int tid = threadIdx.x;
-    constexpr bool CAN_SHARE = pair_has_build<Fam>::value;
+    constexpr bool CAN_SHARE = fam_has_build<Fam>::value;
     const bool shared = CAN_SHARE && a.shared_tab != 0;  // uniform
     T* tabs = rows + a.n_layers * a.tile_stride;
     T* corr = tabs + (shared ? a.n_layers : 64) * a.tab + tid * a.scratch;
@@ -407,53 +403,24 @@ __global__ void __launch_bounds__(64) pair_mchain_kernel(const MPairArgs<T, type
     }
 }
 
-static bool pair_spline_ok(const jf_spline_opts& s) {
-    return s.num_bins >= 1 && s.num_bins <= JF_SPLINE_CAP && s.n_w >= 0 && s.n_h >= 0 && s.n_d >= 0 && (s.smooth == 0 || s.num_bins <= 3);
-}
-// the option limits of the chain entry points (manifold_kernels.hip: CHECK_R .. CHECK_V)
-static bool pair_layer_ok(const jf_r_layer& L) { return pair_spline_ok(L.sp); }
-static bool pair_layer_ok(const jf_o_layer& L) { return pair_spline_ok(L.sp); }
-static bool pair_layer_ok(const jf_m_layer&) { return true; }
-static bool pair_layer_ok(const jf_f_layer& L) {
-    if (L.n_vertical < 0 || L.n_vertical > JF_MAX_NESTED || L.n_circular < 0 || L.n_circular > JF_MAX_NESTED) return false;
-    for (int j = 0; j < L.n_vertical; ++j) if (!pair_spline_ok(L.vertical[j].sp)) return false;
-    for (int j = 0; j < L.n_circular; ++j) if (!pair_spline_ok(L.circular[j].sp)) return false;
-    return true;
-}
-static bool pair_layer_ok(const jf_v_layer& L) { return L.exp_map_type >= 0 && L.exp_map_type <= JF_V_SPLINES; }
-
 template <typename T, class Fam>
 static int grid_mchain(const T* x, int64_t xs, int64_t xgs, const T* params, int64_t ps, int64_t n_groups, int32_t J, int32_t N, int32_t i0, int32_t i1,
                        int32_t n_layers, const typename Fam::CLayer* layers, T* tile, int32_t* status, void* stream) {
-    if (!x || !tile || !layers || n_layers < 1 || n_layers > JF_MAX_MCHAIN || xs < Fam::DIM || ps < 0) return JF_ERR_BADARG;
+    if (!x || !tile || xs < Fam::DIM || ps < 0) return JF_ERR_BADARG;
     PairDims pd{};
     int rc = pair_dims(n_groups, J, N, xgs, i0, i1, pd);
     if (rc != JF_OK) return rc;
+    ChainPlan<Fam> plan;
+    rc = plan_chain<Fam>(layers, n_layers, plan);
+    if (rc != JF_OK) return rc;
+    if (plan.P > 0 && !params) return JF_ERR_BADARG;
     MPairArgs<T, typename Fam::CLayer> a{};
-    a.x = x; a.xs = xs; a.params = params; a.ps = ps; a.n_layers = n_layers; a.dim = Fam::DIM; a.status = status;
-    int col = 0, maxp = 0;
-    for (int l = 0; l < n_layers; ++l) {
-        if (!pair_layer_ok(layers[l])) return JF_ERR_UNSUPPORTED;
-        if (!Fam::sane(layers[l])) return JF_ERR_BADARG;
-        a.L[l] = layers[l];
-        const int n = Fam::row_len(layers[l]);
-        a.col0[l] = col; a.ncols[l] = n;
-        col += n;
-        if (n > maxp) maxp = n;
-    }
-    if (col > 0 && !params) return JF_ERR_BADARG;
-    a.tile_stride = padded_stride<T>(maxp > 0 ? maxp : 1);
-    if constexpr (std::is_same<Fam, FFam>::value) {
-        for (int l = 0; l < n_layers; ++l) {
-            if (!layers[l].correlated) continue;
-            if (layers[l].corr_hidden < 1 || layers[l].corr_rank < 0 || FFam::corr_out(layers[l]) + layers[l].corr_rank > JF_CORR_SCRATCH - 1)
-                return JF_ERR_UNSUPPORTED;
-            a.scratch = JF_CORR_SCRATCH;
-        }
-    }
-    for (int l = 0; l < n_layers; ++l)
-        if (Fam::needs_tab(layers[l])) { const int w = fam_tab_words<Fam>::of(layers[l]); a.tab = w > a.tab ? w : a.tab; }
-    a.shared_tab = (pair_has_build<Fam>::value && a.tab > 0) ? 1 : 0;
+    a.x = x; a.xs = xs; a.params = params; a.ps = ps; a.n_layers = n_layers; a.dim = plan.dim; a.status = status;
+    for (int l = 0; l < n_layers; ++l) { a.L[l] = layers[l]; a.col0[l] = plan.col0[l]; a.ncols[l] = plan.ncols[l]; }
+    a.tile_stride = padded_stride<T>(plan.max_row > 0 ? plan.max_row : 1);
+    a.scratch = plan.corr;
+    a.tab = plan.tab;
+    a.shared_tab = (fam_has_build<Fam>::value && a.tab > 0) ? 1 : 0;
     const size_t lds = ((size_t)n_layers * a.tile_stride + (size_t)(a.shared_tab ? n_layers : 64) * a.tab + (size_t)64 * a.scratch) * sizeof(T);
     if (lds > JF_LDS_WG_MAX) return JF_ERR_UNSUPPORTED;
     if (n_groups == 0 || pd.ni == 0) return JF_OK;

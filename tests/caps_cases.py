@@ -7,9 +7,9 @@ source lines they restate, and the GPU tests run the cases these functions class
 parameter tile of per-sample parameters in LDS where P * 64 * sizeof(T) <= 160 KiB and reads the rows from global memory above.
 
 Manifold adjoints, two launch functions:
-  * mchain_rev (csrc/manifold_rev_kernels.hip:273-338) serves 'r', 'o', 'm' and every 'f' with a nested spline or the correlated MLP;
-  * mchain_bwd (csrc/manifold_bwd_kernels.hip:928-1033) serves 'v' (the staged kernel), and the generic dual-number replay serves 'f' layers
-    without nested flows (manifold_rev_kernels.hip:348-355, prefers_dual) -- the only chains that take its four-direction "wide" form.
+  * mchain_rev (csrc/manifold_rev_kernels.hip:261-320) serves 'r', 'o', 'm' and every 'f' with a nested spline or the correlated MLP;
+  * mchain_bwd (csrc/manifold_bwd_kernels.hip:911-991) serves 'v' (the staged kernel), and the generic dual-number replay serves 'f' layers
+    without nested flows (manifold_rev_kernels.hip:329-336, prefers_dual) -- the only chains that take its four-direction "wide" form.
 Both halve the rows of a workgroup 64 -> 32 -> 16 -> 8 -> 4 until the LDS fits and decline (JF_ERR_UNSUPPORTED) when four rows do not.
 
 What ties this to the library: NOTHING at run time keeps rev_rows() / dual_rows() in step with the C side.  The kernels compute the same result
@@ -145,23 +145,23 @@ def rot_len(hh, E):
 
 
 def _r_terms(L):
-    """'r': jf_manifold.h:76 (tab_words) and jf_manifold_adj.h:207-210 (dual_row, dual_tab, scr_words, corr_words)"""
+    """'r': jf_manifold.h:85 (tab_words) and jf_manifold_adj.h:207-210 (dual_row, dual_tab, scr_words, corr_words)"""
     hand = L.sp.smooth == 0                                          # spline_hand_adjoint, jf_manifold_adj.h:160
     tab = spline_tab_words(L.sp.num_bins)
     return {"tab": tab, "scr": tab, "corr": 0, "drow": 0 if hand else spline_row_len(L.sp), "dtab": 0 if hand else tab}
 
 
 def _o_terms(L):
-    """'o': jf_manifold.h:125 and jf_manifold_adj.h:265-271"""
+    """'o': jf_manifold.h:135 and jf_manifold_adj.h:265-271"""
     hand = L.sp.smooth == 0 or L.sp.num_bins == 2                    # circ_hand_adjoint, jf_manifold_adj.h:161
     tab = spline_tab_words(L.sp.num_bins)
     return {"tab": tab, "scr": tab, "corr": 0, "drow": max(rot_len(L.hh_iter, 2), 0 if hand else spline_row_len(L.sp)), "dtab": 0 if hand else tab}
 
 
 def _f_terms(L):
-    """'f': jf_manifold.h:368-373 and jf_manifold_adj.h:414-432: the largest of the nested splines' terms"""
+    """'f': jf_manifold.h:386-391 and jf_manifold_adj.h:414-432: the largest of the nested splines' terms"""
     nested = [_r_terms(L.vertical[i]) for i in range(L.n_vertical)] + [_o_terms(L.circular[i]) for i in range(L.n_circular)]
-    n_kappa = 1 if L.kappa_mode <= 2 else 0                          # FFam::n_kappa, jf_manifold.h:335
+    n_kappa = 1 if L.kappa_mode <= 2 else 0                          # FFam::n_kappa, jf_manifold.h:347
     return {"tab": max([1] + [t["tab"] for t in nested]), "scr": max([0] + [t["scr"] for t in nested]), "corr": 2 * JF_CORR_SCRATCH if L.correlated else 0,
             "drow": max([rot_len(L.hh_iter, 3) + n_kappa] + [t["drow"] for t in nested]), "dtab": max([0] + [t["dtab"] for t in nested])}
 
@@ -175,12 +175,12 @@ _TERMS = {"r": _r_terms, "o": _o_terms, "f": _f_terms, "m": _m_terms}
 
 
 def f_prefers_dual(structs):
-    """manifold_rev_kernels.hip:348-355: 'f' layers without nested flows and without the correlated MLP go to the dual-number replay"""
+    """manifold_rev_kernels.hip:329-336: 'f' layers without nested flows and without the correlated MLP go to the dual-number replay"""
     return all(L.n_vertical == 0 and L.n_circular == 0 and not L.correlated for L in structs)
 
 
 def rev_rows(fam, structs, P, itemsize, bcast):
-    """manifold_rev_kernels.hip:273-338 (mchain_rev) -> ("shared" | 64 | 32 | 16 | 8 | 4 | "declined", LDS bytes).  structs: the chain's C layer
+    """manifold_rev_kernels.hip:261-320 (mchain_rev) -> ("shared" | 64 | 32 | 16 | 8 | 4 | "declined", LDS bytes).  structs: the chain's C layer
     descriptors, P: its parameter row length (the sum of the layers' total_param_num)"""
     terms = [_TERMS[fam](L) for L in structs]
     scr = max(t["scr"] for t in terms)                             # :281-285; the forward sweep's tables live in the same scratch, :297-298
@@ -209,11 +209,11 @@ def rev_rows(fam, structs, P, itemsize, bcast):
     return ("declined" if lds > M_LDS_CAP else rows), lds          # :329
 
 
-JF_V_ROT_MAX, JF_V_G, JF_SPLINE_TAB = 12, 16, 53                   # manifold_bwd_kernels.hip:307-308, jf_spline.h:35
+JF_V_ROT_MAX, JF_V_G, JF_SPLINE_TAB = 12, 16, 53                   # manifold_bwd_kernels.hip:297-298, jf_spline.h:35
 
 
 def dual_rows(fam, structs, P, itemsize, bcast):
-    """manifold_bwd_kernels.hip:967-997 (mchain_bwd) for the chains that reach it: 'v' (the staged kernel: every layer's rotation row within
+    """manifold_bwd_kernels.hip:929-969 (mchain_bwd) for the chains that reach it: 'v' (the staged kernel: every layer's rotation row within
     JF_V_ROT_MAX, :953-966) and 'f' without nested flows (the generic kernel, no tables, no scratch)
     -> ("64 wide" | 64 | 32 | 16 | 8 | 4 | "declined", LDS bytes)"""
     n = len(structs)

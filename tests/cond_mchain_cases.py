@@ -77,7 +77,7 @@ KAPPA_MEASURED = {("f", "float32"): 255.0,     # fwd, f K1 9 H 20, B 257 (one ro
                   ("r", "float32"): 0.4516,    # fwd, r5 K1 9 H 20
                   ("r", "float64"): 0.8161}    # inv, r5 K1 9 H 20, B 129
 # The families that rotate ('f', and 'o' with its default add_rotation) owe their figure to single rows: a rotation goes through the embedding
-# and back through acos (csrc/jf_sphere.h:47-53 azimuth, :79-83 eucl_to_s2; jf_manifold.h:89-101 s1_rotate / s2_rotate), which costs u |cot| of
+# and back through acos (csrc/jf_sphere.h:47-53 azimuth, :79-83 eucl_to_s2; jf_manifold.h:98-110 s1_rotate / s2_rotate), which costs u |cot| of
 # the INTERMEDIATE angle -- a conditioning UNIT cannot see, since it perturbs the chain's ends only.  One row in a few hundred lands within 1e-2
 # of an intermediate 0 or pi; which one depends on the draw ('m' and 'r' do not rotate here: their figures stayed below 5.1 over three draws).
 KAPPA = {("f", "float32"): 1024.0, ("f", "float64"): 1.0, ("m", "float32"): 16.0, ("m", "float64"): 8.0,
@@ -223,7 +223,7 @@ class Reference:
 # ------------------------------------------------------------------------------------------------------------------------------------------
 # launch restatement: cond_mchain() of csrc/cond_manifold_kernels.hip
 def _tab_words(fam, L):
-    """fam_tab_words<Fam>::of, jf_manifold.h:50-51: the family's tab_words where it has one ('r' :76, 'o' :125, 'f' :368-373), else JF_SPLINE_TAB"""
+    """fam_tab_words<Fam>::of, jf_manifold.h:55-56: the family's tab_words where it has one ('r' :85, 'o' :135, 'f' :386-391), else JF_SPLINE_TAB"""
     if fam in "ro":
         return spline_tab_words(L.sp.num_bins)
     if fam == "f":
@@ -233,24 +233,24 @@ def _tab_words(fam, L):
 
 
 def _n_bins(fam, L):
-    """Fam::n_bins, jf_manifold.h:74 ('r'), :123 ('o'), :237 ('m'), :366 ('f')"""
+    """Fam::n_bins, jf_manifold.h:83 ('r'), :133 ('o'), :248 ('m'), :384 ('f')"""
     return 1 if fam in "ro" else 0 if fam == "m" else L.n_vertical + L.n_circular
 
 
 def cm_lds_bytes(fam, structs, K1, N, itemsize):
-    """cond_manifold_kernels.hip:50-65: the dynamic LDS of one workgroup"""
-    np_ = (N + 15) // 16 * 16                                      # :50
-    tile_stride = np_ + 1                                          # :51
-    tab = 0                                                        # :53-59
+    """cond_manifold_kernels.hip:48-58: the dynamic LDS of one workgroup"""
+    np_ = (N + 15) // 16 * 16                                      # :48
+    tile_stride = np_ + 1                                          # :49
+    tab = 0                                                        # :51 (the plan's tab, jf_mchain_plan.h)
     if sum(_n_bins(fam, L) for L in structs) > 0:
         tab = max([1] + [_tab_words(fam, L) for L in structs])
-    ldk = (K1 + 3) // 4 * 4 + 1                                    # :60
-    NT = 256 if itemsize == 4 else 128                             # :61
-    return (CM_HMAX * ldk + CM_HMAX + np_ * (CM_HMAX + 1) + np_ + 8 + NT * ldk + NT * tile_stride + NT * tab) * itemsize      # :64-65
+    ldk = (K1 + 3) // 4 * 4 + 1                                    # :53
+    NT = 256 if itemsize == 4 else 128                             # :54
+    return (CM_HMAX * ldk + CM_HMAX + np_ * (CM_HMAX + 1) + np_ + 8 + NT * ldk + NT * tile_stride + NT * tab) * itemsize      # :57-58
 
 
 def cm_decision(fam, structs, K1, H, N, itemsize):
-    """"launch" or "declined" (JF_ERR_UNSUPPORTED): cond_manifold_kernels.hip:36 (K1, H), :44 (a correlated 'f' layer), :46 (N), :66 (LDS)"""
+    """"launch" or "declined" (JF_ERR_UNSUPPORTED): cond_manifold_kernels.hip:37 (K1, H), :40 (a correlated 'f' layer), :42 (N), :59 (LDS)"""
     if K1 > CM_K1MAX or H > CM_HMAX:
         return "declined"
     if fam == "f" and any(L.correlated for L in structs):

@@ -97,14 +97,14 @@ def test_bar_rejects_the_mutants(fam, dtype):
 # ------------------------------------------------------------------------------------------------------------------------------ 'f' log-prob at large kappa
 def test_f_log_prob_loss_at_large_kappa_is_the_float32_format():
     """Why float32 'f' log-prob leaves the bar between W2 x 2 and W2 x 4 (test_gpu_cond_mchain.py, W2_JUST_OUTSIDE), shown on that test's own
-    rows with a float32 numpy emulation of csrc/jf_manifold.h:606-617 (FFam::apply_inv_f32; the float64 launch runs other code, inv_head /
+    rows with a float32 numpy emulation of csrc/jf_manifold.h:624-635 (FFam::apply_inv_f32; the float64 launch runs other code, inv_head /
     inv_tail, so it cannot serve as the control for this entry point).
 
-    With zs = -1 (the default inverse_z_scaling) the von-Mises-Fisher step :609 is ret = (1 + e2k - 2 E) / (1 - e2k),
-    E = exp(-kappa (1 + cos theta')): ret = 1 - 2 E up to O(e2k).  kappa = exp(parameter) (:339): a parameter of 2.7 is kappa = 14, of 5.3
+    With zs = -1 (the default inverse_z_scaling) the von-Mises-Fisher step :627 is ret = (1 + e2k - 2 E) / (1 - e2k),
+    E = exp(-kappa (1 + cos theta')): ret = 1 - 2 E up to O(e2k).  kappa = exp(parameter) (:351): a parameter of 2.7 is kappa = 14, of 5.3
     kappa = 194, and E falls below float32's spacing under 1 (2^-24) as soon as kappa (1 + cos theta') > 16.6.  Then ret IS 1 in float32,
-    safe_cos (:611, :614) and the chart's own clamp (:616, 1e-6) put it at 1 - 1e-6, and lh = log(om / 2) (:617) is log((1 - fl(1 - 1e-6)) / 2) = -14.4955 whatever
-    E was: that constant goes into the log-det (:618) and the radius sqrt(-2 lh) (:619).  Above the spacing, om = 1 - ret (:616) keeps
+    safe_cos (:629, :632) and the chart's own clamp (:634, 1e-6) put it at 1 - 1e-6, and lh = log(om / 2) (:635) is log((1 - fl(1 - 1e-6)) / 2) = -14.4955 whatever
+    E was: that constant goes into the log-det (:636) and the radius sqrt(-2 lh) (:637).  Above the spacing, om = 1 - ret (:634) keeps
     u / om of relative accuracy.  Asserted here:
       * where om >= 2^-20 the emulation is within (8 + 3 |arg| + 3 kappa) / (1 - e2k) u / om of the float64 value of lh, arg = kappa (-cos theta' - 1)
         (8: the roundings of the numerator, the reciprocal and the quotient at size <= 2; the exponent's absolute error is E's relative
@@ -113,7 +113,7 @@ def test_f_log_prob_loss_at_large_kappa_is_the_float32_format():
       * at W2 x 1 and x 2 every row is there (the smallest om: 4e-4 and 7e-4 -- the rows drawn 1e-3 from a pole);
       * at W2 x 4 and x 8 rows with om < 2^-24 exist (2 and 28 of 257), the emulation gives exactly that constant on each and is off by more
         than 3 in lh (6.3 at x 4, 9.2 at x 8).
-    The generic float32 form loses the same: inv_head :421 forms the same ret, which is 1 before inv_tail :429-431 sees it (its clamp is
+    The generic float32 form loses the same: inv_head :439 forms the same ret, which is 1 before inv_tail :447-449 sees it (its clamp is
     EPS_COS = 1e-7: another constant, the same loss).  Carrying log(1 - ret) = log(2 E) = log 2 - kappa (1 + cos theta') instead of ret
     would keep it, in a kernel that no longer evaluates the reference's formula."""
     f, u = np.float32, 2.0 ** -24
@@ -132,11 +132,11 @@ def test_f_log_prob_loss_at_large_kappa_is_the_float32_format():
         om64 = 1.0 - (-((1.0 + e2k - 2.0 * E) / (-1.0 + e2k)))
         lh64 = np.log(np.clip(om64, 1e-10, None) * 0.5)               # (the oracle's own margin, sphere_base.py:21-38)
         k32, p32 = kappa.astype(f), prev.astype(f)
-        e2 = np.exp(f(-2) * k32)                                        # :606
-        ret = f(-1) * ((f(1) + e2 - f(2) * np.exp(k32 * (f(-1) * p32 - f(1)))) * (f(1) / (f(-1) + e2)))        # :609
-        ret = np.clip(ret, f(-1) + f(1e-7), f(1) - f(1e-7))           # :611, :614 (EPS_COS)
-        om = f(1) - np.clip(ret, f(-1) + f(1e-6), f(1) - f(1e-6))     # :616
-        lh32 = np.log(om * f(0.5)).astype(np.float64)                 # :617
+        e2 = np.exp(f(-2) * k32)                                        # :624
+        ret = f(-1) * ((f(1) + e2 - f(2) * np.exp(k32 * (f(-1) * p32 - f(1)))) * (f(1) / (f(-1) + e2)))        # :627
+        ret = np.clip(ret, f(-1) + f(1e-7), f(1) - f(1e-7))           # :629, :632 (EPS_COS)
+        om = f(1) - np.clip(ret, f(-1) + f(1e-6), f(1) - f(1e-6))     # :634
+        lh32 = np.log(om * f(0.5)).astype(np.float64)                 # :635
         d = np.abs(lh32 - lh64)
         kept, lost = om64 >= 2.0 ** -20, om64 < 2.0 ** -24
         worst = float((d[kept] / ((8.0 + 3.0 * np.abs(arg[kept]) + 3.0 * kappa[kept]) / (1.0 - e2k[kept]) * u / om64[kept])).max())

@@ -273,7 +273,7 @@ def test_r_targets_outside_the_interval_are_counted(dtype):
 #                    non-finite rows of 257.  Held to: the float64 entry point meets ITS bar on the same operands with no non-finite row, and
 #                    the float32 launch leaves no non-finite row uncounted and nothing out of range.
 #                    What the float64 control shows: the case is sound, and so is the layers' code where float32 and float64 run the SAME
-#                    code -- every entry point but float32 'f' log-prob, which apply_hot (jf_manifold.h:631-635) sends to the hand-written
+#                    code -- every entry point but float32 'f' log-prob, which apply_hot (jf_manifold.h:649-653) sends to the hand-written
 #                    FFam::apply_inv_f32 (:569-627).  For that one the cause is shown on the CPU instead, on these very rows:
 #                    test_cond_mchain_host.py::test_f_log_prob_loss_at_large_kappa_is_the_float32_format.  kappa = exp(parameter) (:339)
 #                    reaches 14 at 2^2 and 194 at 2^3; the von-Mises-Fisher step :609 is ret = 1 - 2 exp(-kappa (1 + cos theta')) up to
