@@ -5,5 +5,6 @@ All arithmetic runs in hand-written HIP kernels (``libjammy_hip.so``, C ABI in i
 """
 from .main.default import pdf  # noqa: F401
 from .main.fully_amortized import fully_amortized_pdf  # noqa: F401
+from . import sky  # noqa: F401
 
 __version__ = "0.1.0"

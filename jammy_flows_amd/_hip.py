@@ -276,6 +276,27 @@ JF_ANALYSIS_ABI = 1
 HPD_CHUNK = 4096                 # JF_HPD_CHUNK: cells of a tile row that one workgroup reduces (csrc/hpd_kernels.hip)
 _analysis_bound = False
 
+# name -> (argtypes, restype): the sky maps of include/jammy_hip_sky.h (a third header with an ABI number of its own).  Bound on first use by
+# _sky().
+_SIGNATURES_SKY = {"jf_sky_abi_version": ([], ctypes.c_int),
+                   #                      sorted stride G    S     uniq row n_cells counts
+                   "jf_sky_cell_counts": ([_P, _I64, _I64, _I64, _P, _P, _I64, _P, _P], ctypes.c_int),
+                   #                 cell_start offsets G  pix  T   cell_out
+                   "jf_sky_locate": ([_P, _P, _I64, _P, _I64, _P, _P], ctypes.c_int)}
+for _d in ("_f32", "_f64"):
+    #                                       v   stride ncol  B     order pix status
+    _SIGNATURES_SKY["jf_sky_vec2pix" + _d] = ([_P, _I64, _I32, _I64, _I32, _P, _P, _P], ctypes.c_int)
+    #                                            uniq M    ncol  out stride
+    _SIGNATURES_SKY["jf_sky_cell_centres" + _d] = ([_P, _I64, _I32, _P, _I64, _P], ctypes.c_int)
+    #                                         lp  stride logw logw_stride G M
+    _SIGNATURES_SKY["jf_sky_hpd_stats" + _d] = ([_P, _I64, _P, _I64, _I64, _I64, _P, _P, _P, _P, _I64, _P], ctypes.c_int)
+    _SIGNATURES_SKY["jf_sky_hpd_mass" + _d] = ([_P, _I64, _P, _I64, _I64, _I64, _P, _I32, _P, _P, _P, _I64, _P], ctypes.c_int)
+    _SIGNATURES_SKY["jf_sky_hpd_levels" + _d] = ([_P, _I64, _P, _I64, _I64, _I64, _D, _I32, _P, _P, _P, _P, _I64, _P], ctypes.c_int)
+    _SIGNATURES_SKY["jf_sky_region_volume" + _d] = ([_P, _I64, _P, _I64, _I64, _I64, _P, _I32, _P, _P, _I64, _P], ctypes.c_int)
+JF_SKY_ABI = 1
+SKY_MAX_ORDER = 29               # JF_SKY_MAX_ORDER
+_sky_bound = False
+
 
 def exported_symbols():
     """all symbols include/jammy_hip.h declares (used by the CPU-side ABI test)."""
@@ -313,24 +334,42 @@ def lib():
     return _lib
 
 
+def _bind_header(table, header, abi_fn, abi, what):
+    """bind the entry points of one of the separately versioned headers (name -> (argtypes, restype)) and check its ABI number -> the library;
+    a library built before the header existed raises HipUnavailable with the rebuild hint."""
+    l = lib()
+    for name, (argtypes, restype) in table.items():
+        fn = getattr(l, name, None)
+        if fn is None:
+            raise HipUnavailable("%s does not export %s (include/%s): it is older than this package -- rebuild it with "
+                                 "`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C jammy_flows_amd/csrc`)" % (LIB_PATH, name, header))
+        fn.argtypes = argtypes
+        fn.restype = restype
+    have = int(getattr(l, abi_fn)())
+    if have != abi:
+        raise HipUnavailable("%s has %s ABI %d, this package needs %d -- rebuild it with `python -c 'import __graft_entry__ as g; g.build()'`"
+                             % (LIB_PATH, what, have, abi))
+    return l
+
+
 def _analysis():
     """the library with the entry points of include/jammy_hip_analysis.h bound (once, on first use); a library built before they existed
     raises HipUnavailable with the rebuild hint."""
     global _analysis_bound
-    l = lib()
     if _analysis_bound:
-        return l
-    for name, (argtypes, restype) in _SIGNATURES_ANALYSIS.items():
-        fn = getattr(l, name, None)
-        if fn is None:
-            raise HipUnavailable("%s does not export %s (include/jammy_hip_analysis.h): it is older than this package -- rebuild it with "
-                                 "`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C jammy_flows_amd/csrc`)" % (LIB_PATH, name))
-        fn.argtypes = argtypes
-        fn.restype = restype
-    if int(l.jf_analysis_abi_version()) != JF_ANALYSIS_ABI:
-        raise HipUnavailable("%s has analysis ABI %d, this package needs %d -- rebuild it with `python -c 'import __graft_entry__ as g; g.build()'`"
-                             % (LIB_PATH, int(l.jf_analysis_abi_version()), JF_ANALYSIS_ABI))
+        return lib()
+    l = _bind_header(_SIGNATURES_ANALYSIS, "jammy_hip_analysis.h", "jf_analysis_abi_version", JF_ANALYSIS_ABI, "analysis")
     _analysis_bound = True
+    return l
+
+
+def _sky():
+    """the same for include/jammy_hip_sky.h"""
+    global _sky_bound
+    if _sky_bound:
+        return lib()
+    l = _bind_header(_SIGNATURES_SKY, "jammy_hip_sky.h", "jf_sky_abi_version", JF_SKY_ABI, "sky")
+    _sky_bound = True
     return l
 
 
@@ -1806,6 +1845,85 @@ def hpd_levels(tile, q, log_norm, logw=None):
     _launch("jf_hpd_levels" + _suffix(tile), "hpd", (_ptr(tile), _hpd_row_stride(tile), _ptr(logw), G, M, (ctypes.c_double * Q)(*qs), Q, _ptr(log_norm),
                                                     _ptr(level), _ptr(level_mass), _ptr(scratch), nbytes), dev)
     return level, level_mass
+
+
+def _sky_tile(what, tile, logw, log_norm=None):
+    """_hpd_tile for the entry points of include/jammy_hip_sky.h: logw may also be (G, M), one row of log-volumes per tile row -> (device, tile,
+    logw, its row stride (0 = shared), log_norm)"""
+    _sky()
+    if logw is not None and logw.dim() == 2:
+        if logw.dtype != tile.dtype or tuple(logw.shape) != tuple(tile.shape):
+            raise ValueError("%s: logw must be (M,) or (G, M) = %s of the tile's dtype" % (what, tuple(tile.shape)))
+        require_device(tile, logw)
+        dev, tile, _, log_norm = _hpd_tile(what, tile, None, log_norm)
+        logw = logw.contiguous()
+        return dev, tile, logw, tile.shape[1], log_norm
+    dev, tile, logw, log_norm = _hpd_tile(what, tile, logw, log_norm)
+    return dev, tile, logw, 0, log_norm
+
+
+def sky_hpd_stats(tile, logw=None):
+    """hpd_stats with logw (M,) shared by all rows -- then bit for bit hpd_stats -- or (G, M), one row of log-volumes per tile row
+    (jf_sky_hpd_stats)."""
+    dev, tile, logw, lws, _ = _sky_tile("sky_hpd_stats", tile, logw)
+    G, M = tile.shape
+    log_norm = torch.empty(G, dtype=torch.float64, device=tile.device)
+    max_lp = torch.empty(G, dtype=tile.dtype, device=tile.device)
+    argmax = torch.empty(G, dtype=torch.int64, device=tile.device)
+    scratch, nbytes = _hpd_scratch("sky_hpd_stats", tile, 0)
+    _launch("jf_sky_hpd_stats" + _suffix(tile), "hpd", (_ptr(tile), _hpd_row_stride(tile), _ptr(logw), lws, G, M, _ptr(log_norm), _ptr(max_lp),
+                                                       _ptr(argmax), _ptr(scratch), nbytes), dev)
+    return log_norm, max_lp, argmax
+
+
+def _sky_thresholds(what, tile, thr):
+    require_device(tile, thr)
+    if thr.dim() != 2 or thr.shape[0] != tile.shape[0] or thr.dtype != tile.dtype:
+        raise ValueError("%s: thr must be a (G, T) = (%d, T) tensor of the tile's dtype, got %s %s" % (what, tile.shape[0], tuple(thr.shape), thr.dtype))
+    return thr.contiguous()
+
+
+def sky_hpd_mass(tile, thr, log_norm, logw=None):
+    """hpd_mass with shared (M,) or per-row (G, M) log-volumes (jf_sky_hpd_mass)."""
+    dev, tile, logw, lws, log_norm = _sky_tile("sky_hpd_mass", tile, logw, log_norm)
+    thr = _sky_thresholds("sky_hpd_mass", tile, thr)
+    G, M = tile.shape
+    T = thr.shape[1]
+    mass = torch.empty((G, T), dtype=torch.float64, device=tile.device)
+    scratch, nbytes = _hpd_scratch("sky_hpd_mass", tile, T)
+    _launch("jf_sky_hpd_mass" + _suffix(tile), "hpd", (_ptr(tile), _hpd_row_stride(tile), _ptr(logw), lws, G, M, _ptr(thr), T, _ptr(log_norm),
+                                                      _ptr(mass), _ptr(scratch), nbytes), dev)
+    return mass
+
+
+def sky_hpd_levels(tile, q, log_norm, logw=None):
+    """hpd_levels with shared (M,) or per-row (G, M) log-volumes (jf_sky_hpd_levels)."""
+    dev, tile, logw, lws, log_norm = _sky_tile("sky_hpd_levels", tile, logw, log_norm)
+    G, M = tile.shape
+    qs = [float(v) for v in (q.tolist() if hasattr(q, "tolist") else q)]
+    if not qs or not all(0.0 < v < 1.0 for v in qs):
+        raise ValueError("sky_hpd_levels: credible masses must be a non-empty sequence of numbers in (0, 1), got %s" % (qs,))
+    Q = len(qs)
+    level = torch.empty((G, Q), dtype=tile.dtype, device=tile.device)
+    level_mass = torch.empty((G, Q), dtype=torch.float64, device=tile.device)
+    scratch, nbytes = _hpd_scratch("sky_hpd_levels", tile, Q)
+    _launch("jf_sky_hpd_levels" + _suffix(tile), "hpd", (_ptr(tile), _hpd_row_stride(tile), _ptr(logw), lws, G, M, (ctypes.c_double * Q)(*qs), Q,
+                                                        _ptr(log_norm), _ptr(level), _ptr(level_mass), _ptr(scratch), nbytes), dev)
+    return level, level_mass
+
+
+def sky_region_volume(tile, thr, logw=None):
+    """volume (G, T) float64: volume[g, t] = sum over the cells with tile[g, m] >= thr[g, t] of exp(logw[g, m]) (logw (M,), (G, M), or None: the
+    number of such cells) (jf_sky_region_volume).  -inf and NaN cells are never selected; a NaN threshold selects nothing."""
+    dev, tile, logw, lws, _ = _sky_tile("sky_region_volume", tile, logw)
+    thr = _sky_thresholds("sky_region_volume", tile, thr)
+    G, M = tile.shape
+    T = thr.shape[1]
+    volume = torch.empty((G, T), dtype=torch.float64, device=tile.device)
+    scratch, nbytes = _hpd_scratch("sky_region_volume", tile, T)
+    _launch("jf_sky_region_volume" + _suffix(tile), "hpd", (_ptr(tile), _hpd_row_stride(tile), _ptr(logw), lws, G, M, _ptr(thr), T, _ptr(volume),
+                                                           _ptr(scratch), nbytes), dev)
+    return volume
 
 
 def amlp_stage(x, seg, n_in, n_out, rank, has_bias, act, residual=None):

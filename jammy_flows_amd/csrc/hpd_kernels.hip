@@ -2,9 +2,11 @@
 // highest-posterior-density (HPD) mass above thresholds and the log-density levels of credible regions -- what the reference does on the host
 // with argsort / cumsum / argmax inside coverage_and_or_pdf_scan (main/default.py:2162-2184, 2214-2237).  gfx950, wave64.
 //
-// A tile is G rows x M cells (float or double, row stride >= M) with an optional shared cell log-volume logw (M).  Every term is converted to
-// double and all arithmetic (exp, sums, log) is double for both tile dtypes: the kernels stream the tile once per pass and are bandwidth- or
-// launch-bound, so the software exp is not what they wait for.
+// A tile is G rows x M cells (float or double, row stride >= M) with an optional cell log-volume logw: M values shared by all rows (row stride
+// 0, all that include/jammy_hip_analysis.h offers) or one row of M per tile row (row stride >= M: the jf_sky_hpd_* entry points of
+// include/jammy_hip_sky.h, whose meshes differ from row to row; they also add the selected cells' volume, jf_sky_region_volume).  Every term
+// is converted to double and all arithmetic (exp, sums, log) is double for both tile dtypes: the kernels stream the tile once per pass and are
+// bandwidth- or launch-bound, so the software exp is not what they wait for.
 //
 // Fixed order.  A row is cut into chunks of HPD_CHUNK cells; one workgroup of HPD_THREADS threads reduces one chunk of one row (grid = (chunks,
 // G), so one long row still fills the chip): thread t walks its cells t, t + HPD_THREADS, ... in index order, the 64 lanes of a wave are
@@ -18,6 +20,7 @@
 #include "jf_common.h"
 
 #include "../../include/jammy_hip_analysis.h"
+#include "../../include/jammy_hip_sky.h"
 
 #include <limits>
 
@@ -90,13 +93,14 @@ constexpr int64_t NO_INDEX = std::numeric_limits<int64_t>::max();
 // one chunk of one row -> part[(g * n_chunks + c) * 4 ..]: {m = max(lp + logw), sum exp(lp + logw - m), max lp, first index of max lp as a
 // double's bits}; a NaN sum marks a chunk that holds a NaN or +inf
 template <typename T>
-__global__ void __launch_bounds__(THREADS) stats_chunk_kernel(const T* __restrict__ lp, int64_t stride, const T* __restrict__ logw, int64_t M,
-                                                              double* __restrict__ part) {
+__global__ void __launch_bounds__(THREADS) stats_chunk_kernel(const T* __restrict__ lp, int64_t stride, const T* __restrict__ logw_base,
+                                                              int64_t logw_stride, int64_t M, double* __restrict__ part) {
     __shared__ double sh_a[WAVES], sh_v[WAVES], sh_s[WAVES];
     __shared__ int64_t sh_i[WAVES];
     const int tid = threadIdx.x, lane = tid & (JF_WAVE - 1), wave = tid / JF_WAVE;
     const int64_t g = blockIdx.y, c0 = (int64_t)blockIdx.x * CHUNK;
     const T* row = lp + g * stride;
+    const T* logw = logw_base ? logw_base + g * logw_stride : nullptr;       // (stride 0: one row of log-volumes shared by all tile rows)
     double a[CELLS];
     double amax = NEG_INF, vmax = NEG_INF;
     int64_t imax = NO_INDEX;
@@ -172,16 +176,21 @@ __global__ void __launch_bounds__(JF_WAVE) stats_row_kernel(const double* __rest
 // one chunk of one row against T thresholds -> part[(g * n_chunks + c) * T + t] = sum over the chunk's cells with key(lp) >= key_t of
 // exp(lp + logw - log_norm[g]).  LEVELS = false: key_t = key(thr[g * T + t]) (a NaN threshold selects nothing).  LEVELS = true: T = Q * LEV_FAN
 // candidates of the level search, key_t = prefix[g * Q + t / LEV_FAN] | (t % LEV_FAN + 1) << shift (prefix 0 in the first pass).
-template <typename T, bool LEVELS>
-__global__ void __launch_bounds__(THREADS) mass_chunk_kernel(const T* __restrict__ lp, int64_t stride, const T* __restrict__ logw, int64_t M,
-                                                             const T* __restrict__ thr, const uint64_t* __restrict__ prefix, int32_t n_thr,
-                                                             int32_t Q, int32_t shift, int32_t first, const double* __restrict__ log_norm,
+// VOLUME (with LEVELS = false): the sum is over exp(logw) alone -- the selected cells' volume, not their mass; log_norm is not read, and
+// -inf or NaN cells are never selected.
+template <typename T, bool LEVELS, bool VOLUME = false>
+__global__ void __launch_bounds__(THREADS) mass_chunk_kernel(const T* __restrict__ lp, int64_t stride, const T* __restrict__ logw_base,
+                                                             int64_t logw_stride, int64_t M, const T* __restrict__ thr,
+                                                             const uint64_t* __restrict__ prefix, int32_t n_thr, int32_t Q, int32_t shift,
+                                                             int32_t first, const double* __restrict__ log_norm,
                                                              double* __restrict__ part) {
     __shared__ double sh[TB][WAVES];
     const int tid = threadIdx.x, lane = tid & (JF_WAVE - 1), wave = tid / JF_WAVE;
     const int64_t g = blockIdx.y, c0 = (int64_t)blockIdx.x * CHUNK;
     const T* row = lp + g * stride;
-    const double ln = log_norm[g];
+    const T* logw = logw_base ? logw_base + g * logw_stride : nullptr;
+    double ln = 0.0;
+    if constexpr (!VOLUME) ln = log_norm[g];
     using K = typename Key<T>::type;
     double e[CELLS];
     K key[CELLS];
@@ -192,7 +201,8 @@ __global__ void __launch_bounds__(THREADS) mass_chunk_kernel(const T* __restrict
         const T v = in ? row[m] : (T)NEG_INF;
         const double w = (in && logw) ? (double)logw[m] : 0.0;
         key[i] = (K)Key<T>::of(v);
-        e[i] = in ? exp((double)v + w - ln) : 0.0;
+        if constexpr (VOLUME) e[i] = (in && v > (T)NEG_INF) ? exp(w) : 0.0;
+        else e[i] = in ? exp((double)v + w - ln) : 0.0;
     }
     double* out = part + (g * gridDim.x + blockIdx.x) * (int64_t)n_thr;
     for (int t0 = 0; t0 < n_thr; t0 += TB) {
@@ -263,6 +273,15 @@ __global__ void __launch_bounds__(JF_WAVE) mass_row_kernel(const double* __restr
     if (threadIdx.x == 0) mass[g * n_thr + t] = unit_mass(s, log_norm[g]);
 }
 
+// the same sum without the clip to [0, 1]: a region's volume.  grid (T, G), one wave each
+__global__ void __launch_bounds__(JF_WAVE) volume_row_kernel(const double* __restrict__ part, int64_t n_chunks, int32_t n_thr,
+                                                             double* __restrict__ volume) {
+    const int64_t g = blockIdx.y;
+    const int32_t t = blockIdx.x;
+    const double s = row_mass(part, g, n_chunks, n_thr, t, threadIdx.x);
+    if (threadIdx.x == 0) volume[g * n_thr + t] = s;
+}
+
 // one pass of the level search, grid (Q, G), LEV_FAN + 1 waves each: wave c - 1 sums the chunk partials of candidate prefix | c << shift
 // (row_mass, side by side instead of one after the other); among the candidates (c ascending, masses non-increasing) the largest whose
 // mass still reaches q extends the prefix.  state: prefix keys (G * Q), then their masses (G * Q).  The last pass (shift == 0) writes the
@@ -325,48 +344,50 @@ static int64_t scratch_bytes(int64_t G, int64_t M, int32_t T) {
 }
 
 template <typename T>
-static int check_tile(const T* lp, int64_t stride, int64_t G, int64_t M, int32_t n, const void* scratch, int64_t have) {
+static int check_tile(const T* lp, int64_t stride, int64_t logw_stride, int64_t G, int64_t M, int32_t n, const void* scratch, int64_t have) {
     if (!lp || !scratch || G < 0 || M < 1 || stride < M || n < 0) return JF_ERR_BADARG;
+    if (logw_stride != 0 && logw_stride < M) return JF_ERR_BADARG;          // 0: shared log-volumes; otherwise one row of M per tile row
     const int64_t need = scratch_bytes(G, M, n);
     if (need < 0) return (int)need;
     return have < need ? JF_ERR_BADARG : JF_OK;
 }
 
 template <typename T>
-static int stats(const T* lp, int64_t stride, const T* logw, int64_t G, int64_t M, double* log_norm, T* max_lp, int64_t* argmax, void* scratch,
-                 int64_t scratch_len, void* stream) {
+static int stats(const T* lp, int64_t stride, const T* logw, int64_t logw_stride, int64_t G, int64_t M, double* log_norm, T* max_lp,
+                 int64_t* argmax, void* scratch, int64_t scratch_len, void* stream) {
     if (!log_norm || !max_lp || !argmax) return JF_ERR_BADARG;
-    if (const int rc = check_tile(lp, stride, G, M, 0, scratch, scratch_len)) return rc;
+    if (const int rc = check_tile(lp, stride, logw_stride, G, M, 0, scratch, scratch_len)) return rc;
     if (G == 0) return JF_OK;
     const int64_t nc = chunks_of(M);
     hipStream_t st = (hipStream_t)stream;
     double* part = static_cast<double*>(scratch);
-    jf::launch(stats_chunk_kernel<T>, dim3((unsigned)nc, (unsigned)G), dim3(THREADS), 0, st, lp, stride, logw, M, part);
+    jf::launch(stats_chunk_kernel<T>, dim3((unsigned)nc, (unsigned)G), dim3(THREADS), 0, st, lp, stride, logw, logw_stride, M, part);
     jf::launch(stats_row_kernel<T>, dim3((unsigned)G), dim3(JF_WAVE), 0, st, part, nc, log_norm, max_lp, argmax);
     return check_launch();
 }
 
 template <typename T>
-static int mass(const T* lp, int64_t stride, const T* logw, int64_t G, int64_t M, const T* thr, int32_t n_thr, const double* log_norm, double* out,
-                void* scratch, int64_t scratch_len, void* stream) {
+static int mass(const T* lp, int64_t stride, const T* logw, int64_t logw_stride, int64_t G, int64_t M, const T* thr, int32_t n_thr,
+                const double* log_norm, double* out, void* scratch, int64_t scratch_len, void* stream) {
     if (!thr || !log_norm || !out) return JF_ERR_BADARG;
-    if (const int rc = check_tile(lp, stride, G, M, n_thr, scratch, scratch_len)) return rc;
+    if (const int rc = check_tile(lp, stride, logw_stride, G, M, n_thr, scratch, scratch_len)) return rc;
     if (n_thr > (1 << 30)) return JF_ERR_UNSUPPORTED;              // (grid.x of the row kernel, 32-bit threshold indices)
     if (G == 0 || n_thr == 0) return JF_OK;
     const int64_t nc = chunks_of(M);
     hipStream_t st = (hipStream_t)stream;
     double* part = static_cast<double*>(scratch);
-    jf::launch(mass_chunk_kernel<T, false>, dim3((unsigned)nc, (unsigned)G), dim3(THREADS), 0, st, lp, stride, logw, M, thr, (const uint64_t*)nullptr,
+    jf::launch(mass_chunk_kernel<T, false>, dim3((unsigned)nc, (unsigned)G), dim3(THREADS), 0, st, lp, stride, logw, logw_stride, M, thr,
+               (const uint64_t*)nullptr,
                n_thr, 0, 0, 0, log_norm, part);
     jf::launch(mass_row_kernel, dim3((unsigned)n_thr, (unsigned)G), dim3(JF_WAVE), 0, st, part, nc, n_thr, log_norm, out);
     return check_launch();
 }
 
 template <typename T>
-static int levels(const T* lp, int64_t stride, const T* logw, int64_t G, int64_t M, const double* q, int32_t Q, const double* log_norm, T* level,
-                  double* level_mass, void* scratch, int64_t scratch_len, void* stream) {
+static int levels(const T* lp, int64_t stride, const T* logw, int64_t logw_stride, int64_t G, int64_t M, const double* q, int32_t Q,
+                  const double* log_norm, T* level, double* level_mass, void* scratch, int64_t scratch_len, void* stream) {
     if (!log_norm || !level || !level_mass || (Q > 0 && !q)) return JF_ERR_BADARG;
-    if (const int rc = check_tile(lp, stride, G, M, Q, scratch, scratch_len)) return rc;
+    if (const int rc = check_tile(lp, stride, logw_stride, G, M, Q, scratch, scratch_len)) return rc;
     for (int32_t j = 0; j < Q; ++j)
         if (!(q[j] > 0.0 && q[j] < 1.0)) return JF_ERR_BADARG;
     if (G == 0 || Q == 0) return JF_OK;
@@ -382,12 +403,31 @@ static int levels(const T* lp, int64_t stride, const T* logw, int64_t G, int64_t
         for (int32_t j = 0; j < MAX_Q; ++j) qa.q[j] = j < nq ? q[q0 + j] : 0.5;
         for (int32_t shift = Key<T>::BITS - LEV_BITS; shift >= 0; shift -= LEV_BITS) {
             const int32_t first = shift == Key<T>::BITS - LEV_BITS;
-            jf::launch(mass_chunk_kernel<T, true>, dim3((unsigned)nc, (unsigned)G), dim3(THREADS), 0, st, lp, stride, logw, M, (const T*)nullptr,
+            jf::launch(mass_chunk_kernel<T, true>, dim3((unsigned)nc, (unsigned)G), dim3(THREADS), 0, st, lp, stride, logw, logw_stride, M,
+                       (const T*)nullptr,
                        (const uint64_t*)prefix, nq * LEV_FAN, nq, shift, first, log_norm, part);
             jf::launch(level_step_kernel<T>, dim3((unsigned)nq, (unsigned)G), dim3(STEP_THREADS), 0, st, (const double*)part, nc, nq, qa, shift, first,
                        prefix, pmass, log_norm, level + q0, level_mass + q0, Q);
         }
     }
+    return check_launch();
+}
+
+// volume[g, t] = sum over { m : lp[g, m] >= thr[g, t] } of exp(logw[g, m]): the masked-mass kernel summing volumes, the chunk partials added
+// in chunk order as every other row sum here
+template <typename T>
+static int region_volume(const T* lp, int64_t stride, const T* logw, int64_t logw_stride, int64_t G, int64_t M, const T* thr, int32_t n_thr,
+                         double* out, void* scratch, int64_t scratch_len, void* stream) {
+    if (!thr || !out) return JF_ERR_BADARG;
+    if (const int rc = check_tile(lp, stride, logw_stride, G, M, n_thr, scratch, scratch_len)) return rc;
+    if (n_thr > (1 << 30)) return JF_ERR_UNSUPPORTED;
+    if (G == 0 || n_thr == 0) return JF_OK;
+    const int64_t nc = chunks_of(M);
+    hipStream_t st = (hipStream_t)stream;
+    double* part = static_cast<double*>(scratch);
+    jf::launch(mass_chunk_kernel<T, false, true>, dim3((unsigned)nc, (unsigned)G), dim3(THREADS), 0, st, lp, stride, logw, logw_stride, M, thr,
+               (const uint64_t*)nullptr, n_thr, 0, 0, 0, (const double*)nullptr, part);
+    jf::launch(volume_row_kernel, dim3((unsigned)n_thr, (unsigned)G), dim3(JF_WAVE), 0, st, part, nc, n_thr, out);
     return check_launch();
 }
 
@@ -399,26 +439,49 @@ int jf_analysis_abi_version(void) { return 1; }
 int64_t jf_hpd_scratch_bytes(int64_t G, int64_t M, int32_t T) { return jf::hpd::scratch_bytes(G, M, T); }
 int jf_hpd_stats_f32(const float* lp, int64_t stride, const float* logw, int64_t G, int64_t M, double* log_norm, float* max_lp, int64_t* argmax,
                      void* scratch, int64_t scratch_bytes, void* s) {
-    return jf::hpd::stats<float>(lp, stride, logw, G, M, log_norm, max_lp, argmax, scratch, scratch_bytes, s);
+    return jf::hpd::stats<float>(lp, stride, logw, 0, G, M, log_norm, max_lp, argmax, scratch, scratch_bytes, s);
 }
 int jf_hpd_stats_f64(const double* lp, int64_t stride, const double* logw, int64_t G, int64_t M, double* log_norm, double* max_lp, int64_t* argmax,
                      void* scratch, int64_t scratch_bytes, void* s) {
-    return jf::hpd::stats<double>(lp, stride, logw, G, M, log_norm, max_lp, argmax, scratch, scratch_bytes, s);
+    return jf::hpd::stats<double>(lp, stride, logw, 0, G, M, log_norm, max_lp, argmax, scratch, scratch_bytes, s);
 }
 int jf_hpd_mass_f32(const float* lp, int64_t stride, const float* logw, int64_t G, int64_t M, const float* thr, int32_t T, const double* log_norm,
                     double* mass, void* scratch, int64_t scratch_bytes, void* s) {
-    return jf::hpd::mass<float>(lp, stride, logw, G, M, thr, T, log_norm, mass, scratch, scratch_bytes, s);
+    return jf::hpd::mass<float>(lp, stride, logw, 0, G, M, thr, T, log_norm, mass, scratch, scratch_bytes, s);
 }
 int jf_hpd_mass_f64(const double* lp, int64_t stride, const double* logw, int64_t G, int64_t M, const double* thr, int32_t T, const double* log_norm,
                     double* mass, void* scratch, int64_t scratch_bytes, void* s) {
-    return jf::hpd::mass<double>(lp, stride, logw, G, M, thr, T, log_norm, mass, scratch, scratch_bytes, s);
+    return jf::hpd::mass<double>(lp, stride, logw, 0, G, M, thr, T, log_norm, mass, scratch, scratch_bytes, s);
 }
 int jf_hpd_levels_f32(const float* lp, int64_t stride, const float* logw, int64_t G, int64_t M, const double* q, int32_t Q, const double* log_norm,
                       float* level, double* level_mass, void* scratch, int64_t scratch_bytes, void* s) {
-    return jf::hpd::levels<float>(lp, stride, logw, G, M, q, Q, log_norm, level, level_mass, scratch, scratch_bytes, s);
+    return jf::hpd::levels<float>(lp, stride, logw, 0, G, M, q, Q, log_norm, level, level_mass, scratch, scratch_bytes, s);
 }
 int jf_hpd_levels_f64(const double* lp, int64_t stride, const double* logw, int64_t G, int64_t M, const double* q, int32_t Q, const double* log_norm,
                       double* level, double* level_mass, void* scratch, int64_t scratch_bytes, void* s) {
-    return jf::hpd::levels<double>(lp, stride, logw, G, M, q, Q, log_norm, level, level_mass, scratch, scratch_bytes, s);
+    return jf::hpd::levels<double>(lp, stride, logw, 0, G, M, q, Q, log_norm, level, level_mass, scratch, scratch_bytes, s);
 }
+
+// include/jammy_hip_sky.h: the same reductions with one row of log-volumes per tile row (logw_stride >= M; 0 = shared, the entry points above)
+#define JF_SKY_HPD(SUF, T)                                                                                                                      \
+    int jf_sky_hpd_stats_##SUF(const T* lp, int64_t stride, const T* logw, int64_t logw_stride, int64_t G, int64_t M, double* log_norm,        \
+                               T* max_lp, int64_t* argmax, void* scratch, int64_t scratch_bytes, void* s) {                                    \
+        return jf::hpd::stats<T>(lp, stride, logw, logw_stride, G, M, log_norm, max_lp, argmax, scratch, scratch_bytes, s);                    \
+    }                                                                                                                                           \
+    int jf_sky_hpd_mass_##SUF(const T* lp, int64_t stride, const T* logw, int64_t logw_stride, int64_t G, int64_t M, const T* thr, int32_t n,  \
+                              const double* log_norm, double* mass, void* scratch, int64_t scratch_bytes, void* s) {                           \
+        return jf::hpd::mass<T>(lp, stride, logw, logw_stride, G, M, thr, n, log_norm, mass, scratch, scratch_bytes, s);                       \
+    }                                                                                                                                           \
+    int jf_sky_hpd_levels_##SUF(const T* lp, int64_t stride, const T* logw, int64_t logw_stride, int64_t G, int64_t M, const double* q,        \
+                                int32_t Q, const double* log_norm, T* level, double* level_mass, void* scratch, int64_t scratch_bytes,         \
+                                void* s) {                                                                                                      \
+        return jf::hpd::levels<T>(lp, stride, logw, logw_stride, G, M, q, Q, log_norm, level, level_mass, scratch, scratch_bytes, s);          \
+    }                                                                                                                                           \
+    int jf_sky_region_volume_##SUF(const T* lp, int64_t stride, const T* logw, int64_t logw_stride, int64_t G, int64_t M, const T* thr,        \
+                                   int32_t n, double* volume, void* scratch, int64_t scratch_bytes, void* s) {                                 \
+        return jf::hpd::region_volume<T>(lp, stride, logw, logw_stride, G, M, thr, n, volume, scratch, scratch_bytes, s);                      \
+    }
+JF_SKY_HPD(f32, float)
+JF_SKY_HPD(f64, double)
+#undef JF_SKY_HPD
 }

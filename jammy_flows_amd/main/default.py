@@ -2352,6 +2352,166 @@ class pdf(nn.Module):
             self._report_status(status)
         return (out, samples) if return_samples else out
 
+    # =========================================================================================== sky maps of an s2 block
+    def _sky_arguments(self, what, sub_manifold, conditional_input, labels, credible_masses):
+        """the argument checks sky_map and sky_mesh share, before anything touches a device -> (index of the s2 block, C, credible masses)"""
+        nsub = len(self.pdf_defs_list)
+        k = sub_manifold
+        if k is None:
+            s2 = [i for i, d in enumerate(self.pdf_defs_list) if d == "s2"]
+            if len(s2) != 1:
+                raise ValueError("%s: the pdf has %d s2 sub-manifolds (%s): name one with sub_manifold" % (what, len(s2), "+".join(self.pdf_defs_list)))
+            k = s2[0]
+        elif isinstance(k, bool) or not isinstance(k, int) or not 0 <= k < nsub:
+            raise ValueError("%s: sub_manifold must be an index in [0, %d), got %r" % (what, nsub, k))
+        if self.pdf_defs_list[k] != "s2":
+            raise ValueError("%s: sub-manifold %d is %r, not s2" % (what, k, self.pdf_defs_list[k]))
+        first = conditional_input[0] if type(conditional_input) == list else conditional_input
+        C = 1 if first is None else first.shape[0]
+        if labels is not None and (labels.dim() != 2 or labels.shape[0] != C or labels.shape[1] not in (2, 3)):
+            raise ValueError("%s: labels must be (C, 3) vectors or (C, 2) angles (zenith, azimuth) with C = %d, one row per conditional input, "
+                             "got shape %s" % (what, C, tuple(labels.shape)))
+        qs = None
+        if credible_masses is not None:
+            qs = [float(v) for v in (credible_masses.tolist() if hasattr(credible_masses, "tolist") else credible_masses)]
+            if not qs or not all(0.0 < v < 1.0 for v in qs):
+                raise ValueError("%s: credible_masses must be a non-empty sequence of numbers in (0, 1), got %s" % (what, qs))
+        return k, C, qs
+
+    def _check_sky_mass(self, what, log_norm):
+        bad = (~torch.isfinite(log_norm)).nonzero().reshape(-1).tolist()
+        if bad:
+            raise ValueError("%s: the sky's total mass is not finite for the conditional inputs (rows) %s: log p holds a NaN or an infinity, or "
+                             "no cell carries mass" % (what, bad))
+
+    def sky_map(self, order, sub_manifold=None, conditional_input=None, samplesize=100, labels=None, credible_masses=None,
+                max_tile_elements=2**26, predefined_base=None):
+        """the posterior of an s2 sub-manifold as a full HEALPix map (NESTED scheme, 12 * 4^order equal-area pixels; jammy_flows_amd.sky), for
+        every conditional input, with the numbers a sky localisation reports -> dict of device tensors (C = 1 when unconditional):
+
+            log_prob (C, npix)               log-density per solid angle (embedding coordinates) at the pixel centres, nested order
+            pixel_area () float64            4 pi / npix, steradian
+            log_norm (C,) float64            log sum over the pixels of exp(log_prob) * pixel_area: ~0 once the map resolves the pdf
+            map_pix (C,) int64, map_direction (C, 3), map_log_prob (C,)          the densest pixel (first index among equals)
+          with credible_masses (Q numbers in (0, 1)):
+            levels (C, Q)                    the largest map value t with mass(log_prob >= t) >= q
+            level_masses (C, Q) float64      the mass it reaches
+            areas (C, Q) float64             solid angle of { log_prob >= level }, steradian
+          with labels (C, 3) vectors or (C, 2) angles (zenith, azimuth):
+            label_pix (C,) int64, label_log_prob (C,)        the pixel holding the label and the map's value there
+            coverage (C,) float64            mass of the pixels at least as dense as the label's, over the map's total mass
+
+        sub_manifold: the index of the s2 block; None = the pdf's only one.  The map is marginal_log_prob(sub_manifold, centres, ...) with
+        force_embedding_coordinates: exact for sub-manifold 0, a Monte-Carlo estimate over `samplesize` draws (predefined_base injects
+        their base samples) behind other blocks.  Reductions: csrc/hpd_kernels.hip with the pixels' shared volume -- double arithmetic,
+        fixed order, so a conditional input's results do not depend on the others in the batch."""
+        from .. import sky
+        k, C, qs = self._sky_arguments("sky_map", sub_manifold, conditional_input, labels, credible_masses)
+        if isinstance(order, bool) or not isinstance(order, int) or not 0 <= order <= 13:
+            raise ValueError("sky_map: order must be an integer in [0, 13] (a full map of order 14 has more than 2^31 pixels; sky_mesh resolves "
+                             "finer), got %r" % (order,))
+        npix = 12 * 4 ** order
+        dt, dev = self.obtain_current_dtype_n_device()
+        first = conditional_input[0] if type(conditional_input) == list else conditional_input
+        if first is not None:
+            dt, dev = first.dtype, first.device
+        _hip.require_device(torch.empty(0, device=dev), labels)
+        with torch.no_grad():
+            centres = sky.cell_centres(sky.uniq_of(order, torch.arange(npix, device=dev)), vectors=True, dtype=dt)
+            lp = self.marginal_log_prob(k, centres, conditional_input=conditional_input, samplesize=samplesize, force_embedding_coordinates=True,
+                                        max_tile_elements=max_tile_elements, predefined_base=predefined_base)
+            area = 4.0 * numpy.pi / npix
+            raw_norm, max_lp, argmax = _hip.hpd_stats(lp)            # (the shared volume is one constant: added in double afterwards)
+            log_norm = raw_norm + numpy.log(area)
+            ret = {"log_prob": lp, "pixel_area": torch.tensor(area, dtype=torch.float64, device=lp.device), "log_norm": log_norm,
+                   "map_pix": argmax, "map_direction": centres[argmax.clamp(min=0)], "map_log_prob": max_lp}
+            if qs is not None:
+                ret["levels"], ret["level_masses"] = _hip.hpd_levels(lp, qs, raw_norm)
+                ret["areas"] = _hip.sky_region_volume(lp, ret["levels"]) * area
+            if labels is not None:
+                status = _hip.new_status(lp.device) if self.check_status else None
+                label_pix = sky.vec2pix(order, labels.to(dt), status)
+                self._report_status(status)
+                label_lp = lp.gather(1, label_pix.clamp(min=0)[:, None])
+                ret.update(label_pix=label_pix, label_log_prob=label_lp[:, 0], coverage=_hip.hpd_mass(lp, label_lp, raw_norm)[:, 0])
+            self._check_sky_mass("sky_map", log_norm)
+        return ret
+
+    def sky_mesh(self, sub_manifold=None, conditional_input=None, samplesize=10000, max_entries_per_cell=5, max_order=29, density=None,
+                 marginal_samplesize=100, labels=None, credible_masses=None, predefined_base=None):
+        """the posterior of an s2 sub-manifold on an adaptive multi-order HEALPix mesh per conditional input, refined where the pdf's own
+        samples fall -- the reference's get_multiresolution_evals (helper_fns/plotting/spherical.py:452-549), on the device and batched:
+        `samplesize` samples per conditional input (predefined_base injects their base samples), their order-29 pixels, and
+        sky.build_mesh: a cell is split into four while it holds more than max_entries_per_cell samples and is below max_order
+        -> dict of device tensors (C = 1 when unconditional; the cells of all meshes are flat, row c's at offsets[c]:offsets[c + 1]):
+
+            uniq (total,) int64              NUNIQ ids 4 * 4^order + pix, per row ascending by position in the nested order
+            offsets (C + 1,) int64, counts (total,) int64          samples per cell
+            log_prob (total,)                log-density per solid angle at the cell centres (embedding coordinates)
+            log_area (total,) float64        log solid angle of the cells
+            log_norm (C,) float64            log sum over the row's cells of exp(log_prob + log_area)
+            map_uniq (C,) int64, map_direction (C, 3), map_log_prob (C,)          the densest cell (the first among equals)
+            samples (C, samplesize, 3)       the directions the meshes were built from
+          with credible_masses: levels (C, Q), level_masses (C, Q) float64, areas (C, Q) float64 (steradian), as in sky_map
+          with labels (C, 3) or (C, 2): label_cell (C,) int64 (index into uniq), label_log_prob (C,), coverage (C,) float64
+
+        density: "model" (the default for sub-manifold 0) = marginal_log_prob at the centres -- exact for sub-manifold 0, a Monte-Carlo
+        estimate over marginal_samplesize fresh draws behind other blocks; "samples" (the default otherwise, the reference's
+        use_density_if_possible) = log(count / samplesize) - log_area in float64, -inf for empty cells.  The reductions run on the padded
+        (C, Mmax) tile in float64 (a float32 tile widened, which is exact) with one row of log-areas per conditional input
+        (jf_sky_hpd_* / jf_sky_region_volume of include/jammy_hip_sky.h): a row's results depend on its own cells only."""
+        from .. import sky
+        k, C, qs = self._sky_arguments("sky_mesh", sub_manifold, conditional_input, labels, credible_masses)
+        if density is None:
+            density = "model" if k == 0 else "samples"
+        if density not in ("model", "samples"):
+            raise ValueError("sky_mesh: density must be 'model', 'samples' or None, got %r" % (density,))
+        if isinstance(samplesize, bool) or not isinstance(samplesize, int) or samplesize < 1 or marginal_samplesize < 1:
+            raise ValueError("sky_mesh: samplesize and marginal_samplesize must be positive integers")
+        if isinstance(max_entries_per_cell, bool) or not isinstance(max_entries_per_cell, int) or max_entries_per_cell < 0:
+            raise ValueError("sky_mesh: max_entries_per_cell must be a non-negative integer, got %r" % (max_entries_per_cell,))
+        if isinstance(max_order, bool) or not isinstance(max_order, int) or not 0 <= max_order <= sky.MAX_ORDER:
+            raise ValueError("sky_mesh: max_order must be an integer in [0, %d], got %r" % (sky.MAX_ORDER, max_order))
+        S = samplesize
+        dt, dev, _, data_summary = self._repeat_conditional(conditional_input, S, None, None)
+        _hip.require_device(torch.empty(0, device=dev), labels, predefined_base)
+        with torch.no_grad():
+            samples, _, status = self._sampling_pass(predefined_base, S * C, dt, dev, data_summary, True, False, [])
+            a, b = self.target_dim_indices_embedded[k]
+            dirs = samples[:, a:b].contiguous()
+            pix29 = sky.vec2pix(sky.MAX_ORDER, dirs, status).reshape(C, S)
+            if labels is not None:
+                label_pix = sky.vec2pix(sky.MAX_ORDER, labels.to(dt), status)
+            self._report_status(status)
+            mesh = sky.build_mesh(pix29, max_entries_per_cell, max_order)
+            padded = mesh.padded()
+            real = padded >= 0
+            log_area = sky.cell_log_area(padded)                            # (C, Mmax) float64, 0 in the padding
+            centres = sky.cell_centres(padded, vectors=True, dtype=dt)       # (padding: the north pole, overwritten below)
+            if density == "model":
+                lp = self.marginal_log_prob(k, centres, conditional_input=conditional_input, samplesize=marginal_samplesize,
+                                            force_embedding_coordinates=True)
+            else:
+                lp = torch.log(mesh.padded(mesh.counts, 0).to(torch.float64) / S) - log_area
+            lp = torch.where(real, lp, torch.full_like(lp, float("-inf")))
+            tile = lp.double()
+            log_norm, max_lp, argmax = _hip.sky_hpd_stats(tile, log_area)
+            pick = argmax.clamp(min=0)[:, None]
+            ret = {"uniq": mesh.uniq, "offsets": mesh.offsets, "counts": mesh.counts, "log_prob": lp[real], "log_area": log_area[real],
+                   "log_norm": log_norm, "map_uniq": padded.gather(1, pick)[:, 0], "map_direction": centres[torch.arange(C, device=lp.device), pick[:, 0]],
+                   "map_log_prob": max_lp.to(lp.dtype), "samples": dirs.reshape(C, S, b - a)}
+            if qs is not None:
+                levels, ret["level_masses"] = _hip.sky_hpd_levels(tile, qs, log_norm, log_area)
+                ret["levels"] = levels.to(lp.dtype)
+                ret["areas"] = _hip.sky_region_volume(tile, levels, log_area)
+            if labels is not None:
+                cell = mesh.locate(label_pix[:, None])[:, 0]
+                label_lp = tile.gather(1, (cell - mesh.offsets[:-1]).clamp(min=0)[:, None])
+                ret.update(label_cell=cell, label_log_prob=label_lp[:, 0].to(lp.dtype),
+                           coverage=_hip.sky_hpd_mass(tile, label_lp, log_norm, log_area)[:, 0])
+            self._check_sky_mass("sky_mesh", log_norm)
+        return ret
+
     def _first_marginal_logp(self, x0, data_summary):
         """log-pdf of the first sub-manifold's marginal at x0 (embedding coordinates): block 0 depends on the conditional input alone, so the
         later blocks are filled with ones and only block 0's base log-prob and log-det are kept (as the marginal entropies do)."""
