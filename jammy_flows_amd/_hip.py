@@ -297,6 +297,20 @@ JF_SKY_ABI = 1
 SKY_MAX_ORDER = 29               # JF_SKY_MAX_ORDER
 _sky_bound = False
 
+# name -> (argtypes, restype): the row check of checked sampling, include/jammy_hip_recheck.h (a fourth header with an ABI number of its own).
+# Bound on first use by _recheck().
+_SIGNATURES_RECHECK = {"jf_recheck_abi_version": ([], ctypes.c_int), "jf_recheck_scratch_bytes": ([_I64], _I64)}
+for _d in ("_f32", "_f64"):
+    #                                            x_old stride x_new stride Dx  z_old stride z_new stride Dz  lp_old lp_new B  tol
+    _SIGNATURES_RECHECK["jf_recheck_rows" + _d] = ([_P, _I64, _P, _I64, _I32, _P, _I64, _P, _I64, _I32, _P, _P, _I64, ctypes.c_double,
+                                                    #  dev idx count scratch bytes stream
+                                                    _P, _P, _P, _P, _I64, _P], ctypes.c_int)
+JF_RECHECK_ABI = 1
+RECHECK_CHUNK = 256              # JF_RECHECK_CHUNK: rows of one workgroup of the check (csrc/recheck_kernels.hip)
+RECHECK_SCAN_TILE = 1024         # JF_RECHECK_SCAN_TILE: chunk counts per step of the scan
+RECHECK_MAX_ROWS = 2**31 - 1     # JF_RECHECK_MAX_ROWS
+_recheck_bound = False
+
 
 def exported_symbols():
     """all symbols include/jammy_hip.h declares (used by the CPU-side ABI test)."""
@@ -370,6 +384,16 @@ def _sky():
         return lib()
     l = _bind_header(_SIGNATURES_SKY, "jammy_hip_sky.h", "jf_sky_abi_version", JF_SKY_ABI, "sky")
     _sky_bound = True
+    return l
+
+
+def _recheck():
+    """the same for include/jammy_hip_recheck.h"""
+    global _recheck_bound
+    if _recheck_bound:
+        return lib()
+    l = _bind_header(_SIGNATURES_RECHECK, "jammy_hip_recheck.h", "jf_recheck_abi_version", JF_RECHECK_ABI, "recheck")
+    _recheck_bound = True
     return l
 
 
@@ -1924,6 +1948,55 @@ def sky_region_volume(tile, thr, logw=None):
     _launch("jf_sky_region_volume" + _suffix(tile), "hpd", (_ptr(tile), _hpd_row_stride(tile), _ptr(logw), lws, G, M, _ptr(thr), T, _ptr(volume),
                                                            _ptr(scratch), nbytes), dev)
     return volume
+
+
+def _recheck_pair(what, old, new, B, dtype):
+    """one (old, new) pair of (B, D) arrays of the row check -> (old, new, D) with unit stride inside a row; None or zero width: (None, None, 0)"""
+    if old is None and new is None:
+        return None, None, 0
+    if old is None or new is None or old.dim() != 2 or tuple(old.shape) != tuple(new.shape) or old.shape[0] != B:
+        raise ValueError("recheck_rows: %s_old and %s_new must both be (B, D) = (%d, D) tensors (or both None)" % (what, what, B))
+    if old.dtype != dtype or new.dtype != dtype:
+        raise TypeError("recheck_rows: %s_old / %s_new have dtype %s / %s, the log-pdfs %s" % (what, what, old.dtype, new.dtype, dtype))
+    if old.shape[1] == 0:
+        return None, None, 0
+    return _rowmajor(old), _rowmajor(new), old.shape[1]
+
+
+def _recheck_stride(t):
+    return 0 if t is None else (t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1]))
+
+
+def recheck_rows(x_old, x_new, z_old, z_new, lp_old, lp_new, tol, want_dev=False):
+    """the row check of checked sampling (jf_recheck_rows, include/jammy_hip_recheck.h): dev[b] = the largest |new - old| over row b of the
+    samples x (B, Dx), the base points z (B, Dz) and the log-pdfs lp (B,), NaN where a difference is NaN; row b is flagged iff
+    not dev[b] <= tol -> (idx, count[, dev]): idx a (B,) int64 buffer whose first count[0] entries are the flagged rows in ascending order (the
+    rest is not written), count a one-element int64 device tensor, dev (B,) with want_dev.  Row views with a row stride above their width are
+    read in place; nothing is read back here."""
+    tol = float(tol)
+    if not tol >= 0.0:
+        raise ValueError("recheck_rows: the tolerance must be a number >= 0 (inf is allowed), got %r" % (tol,))
+    if lp_old.dim() != 1 or tuple(lp_new.shape) != tuple(lp_old.shape) or lp_new.dtype != lp_old.dtype:
+        raise ValueError("recheck_rows: lp_old and lp_new must be (B,) tensors of one dtype")
+    suf = _suffix(lp_old)
+    _recheck()
+    dev = require_device(x_old, x_new, z_old, z_new, lp_old, lp_new)
+    B = lp_old.shape[0]
+    x_old, x_new, Dx = _recheck_pair("x", x_old, x_new, B, lp_old.dtype)
+    z_old, z_new, Dz = _recheck_pair("z", z_old, z_new, B, lp_old.dtype)
+    lp_old, lp_new = lp_old.contiguous(), lp_new.contiguous()
+    nbytes = int(_recheck().jf_recheck_scratch_bytes(B))
+    if nbytes < 0:
+        _check(nbytes, "recheck_rows (%d rows)" % B)
+    scratch = torch.empty(nbytes // 8, dtype=torch.int64, device=lp_old.device)
+    idx = torch.empty(B, dtype=torch.int64, device=lp_old.device)
+    count = (torch.empty if B > 0 else torch.zeros)(1, dtype=torch.int64, device=lp_old.device)        # (B == 0: the call touches nothing)
+    dev_out = torch.empty(B, dtype=lp_old.dtype, device=lp_old.device) if want_dev else None
+    _launch("jf_recheck_rows" + suf, "recheck", (_ptr(x_old), _recheck_stride(x_old), _ptr(x_new), _recheck_stride(x_new), Dx,
+                                                 _ptr(z_old), _recheck_stride(z_old), _ptr(z_new), _recheck_stride(z_new), Dz,
+                                                 _ptr(lp_old), _ptr(lp_new), B, tol, _ptr(dev_out), _ptr(idx), _ptr(count), _ptr(scratch), nbytes),
+            dev)
+    return (idx, count, dev_out) if want_dev else (idx, count)
 
 
 def amlp_stage(x, seg, n_in, n_out, rank, has_bias, act, residual=None):

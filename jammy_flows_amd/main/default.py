@@ -21,7 +21,7 @@ from torch import nn
 
 from .. import _hip, autograd, init_fns
 from ..amortizable_mlp import AmortizableMLP
-from ..extra_functions import list_from_str
+from ..extra_functions import list_from_str, recheck_sampling
 from ..flow_options import canonical, check_flow_option, layer_class, obtain_default_options, opts_dict
 from ..layers.euclidean import gaussianization_flow as gfl
 
@@ -435,6 +435,7 @@ class pdf(nn.Module):
         # gradient mode, float64: chains on a low-rank last MLP stage never materialise their (B, P) parameter / gradient blocks
         self.lowrank_chain_training = os.environ.get("JF_LOWRANK_CHAIN_TRAINING", "1") != "0"
         self.use_step_plans = os.environ.get("JF_STEP_PLANS", "0") == "1"      # forward() through recorded step plans (planned_forward)
+        self.last_recheck = None         # what the last checked sampling call redrew (extra_functions.recheck_sampling)
         # float32 log-prob steps of up to merge_max_rows rows that start with an unconditional broadcast g chain and a one-launch `f` block issue
         # the two as ONE launch (csrc/merged_kernels.hip: they overlap each other's latency -- 0.055 -> 0.037 ms at 2^17 rows, 0.228 -> 0.210 at
         # 2^20); 0 = never
@@ -1585,9 +1586,13 @@ class pdf(nn.Module):
     def _obtain_sample(self, conditional_input=None, predefined_target_input=None, samplesize=1, seed=None, amortization_parameters=None,
                        force_embedding_coordinates=False, force_intrinsic_coordinates=False, failsafe_crosscheck_tolerance=None, dtype=None,
                        device=None, only_last=False):
-        """base noise (drawn with numpy on the host like the reference does, or injected) -> (x, base, log_prob, log_prob_base)  (:1533-1707)."""
+        """base noise (drawn with numpy on the host like the reference does, or injected) -> (x, base, log_prob, log_prob_base)  (:1533-1707).
+        With failsafe_crosscheck_tolerance the samples are checked by a round trip and the rows that do not close are drawn again
+        (extra_functions.recheck_sampling; self.last_recheck tells how many)."""
         if failsafe_crosscheck_tolerance:
-            raise NotImplementedError("failsafe_crosscheck_tolerance (recheck_sampling) is outside the MI355X hot path")
+            assert predefined_target_input is None, "Failsafe does not work with predefined input!"
+            if only_last:
+                raise NotImplementedError("failsafe_crosscheck_tolerance together with only_last=True: the round trip runs on the full pdf")
         used = samplesize
         if self.amortize_everything:
             assert amortization_parameters is not None
@@ -1622,7 +1627,12 @@ class pdf(nn.Module):
                                             force_embedding_coordinates=force_embedding_coordinates,
                                             force_intrinsic_coordinates=force_intrinsic_coordinates, only_last=only_last, status=status)
         self._report_status(status)
-        return x, base_ret, log_gauss - log_det, log_gauss          # (one launch; equal to -log_det + log_gauss bit for bit)
+        ret = x, base_ret, log_gauss - log_det, log_gauss           # (one launch; equal to -log_det + log_gauss bit for bit)
+        if failsafe_crosscheck_tolerance:
+            ret = recheck_sampling(self, *ret, failsafe_crosscheck_tolerance=failsafe_crosscheck_tolerance, conditional_input=conditional_input,
+                                   amortization_parameters=amortization_parameters, force_embedding_coordinates=force_embedding_coordinates,
+                                   force_intrinsic_coordinates=force_intrinsic_coordinates, dtype=dt, device=dev)
+        return ret
 
     def _differentiable_sample(self, conditional_input=None, predefined_target_input=None, samplesize=1, seed=None, amortization_parameters=None,
                                force_embedding_coordinates=False, force_intrinsic_coordinates=False, dtype=None, device=None, only_last=False):
@@ -1717,8 +1727,16 @@ class pdf(nn.Module):
     def sample(self, conditional_input=None, samplesize=1, seed=None, allow_gradients=False, amortization_parameters=None,
                force_embedding_coordinates=False, force_intrinsic_coordinates=False, failsafe_crosscheck_tolerance=None, dtype=None,
                device=None, only_last=False):
-        """draw samples -> (x, base, log_prob, log_prob_base)  (:1300-1371)."""
+        """draw samples -> (x, base, log_prob, log_prob_base)  (:1300-1371).  failsafe_crosscheck_tolerance: rows whose round trip through
+        the log-prob direction and back moves the sample, the base point or the log-pdf by more than the tolerance are drawn again
+        (extra_functions.recheck_sampling); not available with only_last or for samples that carry gradients."""
         assert not self.use_as_passthrough_instead_of_pdf
+        if failsafe_crosscheck_tolerance:
+            if only_last:
+                raise NotImplementedError("failsafe_crosscheck_tolerance together with only_last=True: the round trip runs on the full pdf")
+            if allow_gradients and torch.is_grad_enabled():
+                raise NotImplementedError("failsafe_crosscheck_tolerance together with allow_gradients=True under grad mode: redrawn rows "
+                                          "have no differentiable counterpart")
         if allow_gradients and torch.is_grad_enabled():
             return self._differentiable_sample(conditional_input=conditional_input, samplesize=samplesize, seed=seed,
                                                amortization_parameters=amortization_parameters,
@@ -1805,18 +1823,29 @@ class pdf(nn.Module):
         """Monte-Carlo entropy of the pdf and of the marginal pdfs of single sub-manifolds (:2263-2454): -mean log p over `samplesize`
         samples per conditional input; for the marginal of sub-manifold k > 0 the conditional density p(x_k | x_<k) of each of the S
         samples is averaged over the S draws of x_<k (log-mean-exp over an S x S evaluation).  Sampling, the S^2-row log-prob pass and the
-        sample means (jf_segment_reduce) all stay on the device.  `predefined_base` injects the standard-normal base samples (tests)."""
-        if failsafe_crosscheck_tolerance:
-            raise NotImplementedError("failsafe_crosscheck_tolerance (recheck_sampling) is outside the MI355X hot path")
+        sample means (jf_segment_reduce) all stay on the device.  `predefined_base` injects the standard-normal base samples (tests).
+        With failsafe_crosscheck_tolerance the samples are checked by a round trip first and the rows that do not close are drawn again
+        (extra_functions.recheck_sampling, through _sampling_pass on the flagged rows; self.last_recheck tells how many)."""
         S = samplesize
         dt, dev, batch, data_summary = self._repeat_conditional(conditional_input, S, dtype, device)
         for sm in sub_manifolds:
             assert sm == -1 or 0 <= sm < len(self.layer_list)
         out = {}
         with torch.no_grad():
+            blocks = [0] if 0 in sub_manifolds else []
+            if failsafe_crosscheck_tolerance and predefined_base is None:     # the check needs the base samples: drawn here as the pass would
+                predefined_base = torch.randn((S * batch, self.total_base_dim), dtype=dt, device=dev)
             targets, log_pdfs, status = self._sampling_pass(predefined_base, S * batch, dt, dev, data_summary, force_embedding_coordinates,
-                                                            force_intrinsic_coordinates, [0] if 0 in sub_manifolds else [])
+                                                            force_intrinsic_coordinates, blocks)
             self._report_status(status)
+            if failsafe_crosscheck_tolerance:
+                base_lps = {"total": _hip.normal_logp(predefined_base)}
+                for si in blocks:
+                    base_lps[si] = _hip.normal_logp(predefined_base[:, self.base_dim_indices[si][0]:self.base_dim_indices[si][1]])
+                targets, _, log_pdfs, _ = recheck_sampling(self, targets, predefined_base, log_pdfs, base_lps, sub_manifolds=sub_manifolds,
+                                                           failsafe_crosscheck_tolerance=failsafe_crosscheck_tolerance,
+                                                           conditional_input=data_summary, force_embedding_coordinates=force_embedding_coordinates,
+                                                           force_intrinsic_coordinates=force_intrinsic_coordinates, dtype=dt, device=dev)
             if -1 in sub_manifolds:
                 out["total"] = _hip.segment_reduce(log_pdfs["total"], S, "neg_mean")
             for sm in sub_manifolds:
