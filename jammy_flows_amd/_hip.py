@@ -311,6 +311,20 @@ RECHECK_SCAN_TILE = 1024         # JF_RECHECK_SCAN_TILE: chunk counts per step o
 RECHECK_MAX_ROWS = 2**31 - 1     # JF_RECHECK_MAX_ROWS
 _recheck_bound = False
 
+# name -> (argtypes, restype): the refinement steps of density-refined sky maps, include/jammy_hip_sky_refine.h (a fifth header with an ABI number
+# of its own).  Bound on first use by _sky_refine().
+_SIGNATURES_SKY_REFINE = {"jf_sky_refine_abi_version": ([], ctypes.c_int)}
+for _d in ("_f32", "_f64"):
+    #                                                    lp  stride logw stride C     M     K     sel status
+    _SIGNATURES_SKY_REFINE["jf_sky_refine_select" + _d] = ([_P, _I64, _P, _I64, _I64, _I64, _I64, _P, _P, _P], ctypes.c_int)
+    #                                                    uniq lp sel  C     M     K    uniq_out lp_out new_cols status
+    _SIGNATURES_SKY_REFINE["jf_sky_refine_expand" + _d] = ([_P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P], ctypes.c_int)
+    #                                                     lp  stride logw stride C     M   log_norm entropy
+    _SIGNATURES_SKY_REFINE["jf_sky_refine_entropy" + _d] = ([_P, _I64, _P, _I64, _I64, _I64, _P, _P, _P], ctypes.c_int)
+JF_SKY_REFINE_ABI = 1
+SKY_REFINE_CHUNK = 256           # JF_SKY_REFINE_CHUNK: columns per step of a row's walk (csrc/sky_refine_kernels.hip)
+_sky_refine_bound = False
+
 
 def exported_symbols():
     """all symbols include/jammy_hip.h declares (used by the CPU-side ABI test)."""
@@ -394,6 +408,16 @@ def _recheck():
         return lib()
     l = _bind_header(_SIGNATURES_RECHECK, "jammy_hip_recheck.h", "jf_recheck_abi_version", JF_RECHECK_ABI, "recheck")
     _recheck_bound = True
+    return l
+
+
+def _sky_refine():
+    """the same for include/jammy_hip_sky_refine.h"""
+    global _sky_refine_bound
+    if _sky_refine_bound:
+        return lib()
+    l = _bind_header(_SIGNATURES_SKY_REFINE, "jammy_hip_sky_refine.h", "jf_sky_refine_abi_version", JF_SKY_REFINE_ABI, "sky refine")
+    _sky_refine_bound = True
     return l
 
 
@@ -1948,6 +1972,79 @@ def sky_region_volume(tile, thr, logw=None):
     _launch("jf_sky_region_volume" + _suffix(tile), "hpd", (_ptr(tile), _hpd_row_stride(tile), _ptr(logw), lws, G, M, _ptr(thr), T, _ptr(volume),
                                                            _ptr(scratch), nbytes), dev)
     return volume
+
+
+def _refine_tile(what, lp, logw):
+    """the arguments select and entropy share: lp (C, M) float32 / float64, logw float64 (M,), (C, M) or None -> (device, lp, row stride, logw,
+    its row stride (0 = shared))"""
+    if lp.dim() != 2:
+        raise ValueError("%s: expected a (C, M) tile of log-densities, got shape %s" % (what, tuple(lp.shape)))
+    _suffix(lp)
+    C, M = lp.shape
+    if logw is not None and (logw.dtype != torch.float64 or tuple(logw.shape) not in ((M,), (C, M))):
+        raise ValueError("%s: the log-areas must be a float64 (M,) or (C, M) = %s tensor, got %s %s" % (what, (C, M), logw.dtype, tuple(logw.shape)))
+    dev = require_device(lp, logw)
+    _sky_refine()
+    lp = lp.contiguous()
+    lws = 0
+    if logw is not None:
+        lws = M if logw.dim() == 2 else 0
+        logw = logw.contiguous()
+    return dev, lp, M, logw, lws
+
+
+def sky_refine_select(lp, logw, K, status=None):
+    """sel (C, K) int64: per row of lp (C, M) the K columns with the largest key (double)lp + logw, in ascending column order -- larger key
+    first, equal keys to the lower column, NaN as -inf (counted in status), -0.0 as +0.0 (jf_sky_refine_select).  logw: float64 (M,), (C, M)
+    or None."""
+    if isinstance(K, bool) or not isinstance(K, int) or lp.dim() != 2 or not 0 <= K <= lp.shape[1]:
+        raise ValueError("sky_refine_select: K must be an integer in [0, M] for a (C, M) tile, got %r for shape %s" % (K, tuple(lp.shape)))
+    dev, lp, stride, logw, lws = _refine_tile("sky_refine_select", lp, logw)
+    require_device(lp, status)
+    C, M = lp.shape
+    sel = torch.empty((C, K), dtype=torch.int64, device=lp.device)
+    _launch("jf_sky_refine_select" + _suffix(lp), "sky_refine", (_ptr(lp), stride, _ptr(logw), lws, C, M, K, _ptr(sel), _ptr(status)), dev)
+    return sel
+
+
+def sky_refine_expand(uniq, lp, sel, status=None):
+    """(uniq_out (C, M + 3 K), lp_out (C, M + 3 K), new_cols (C, 4 K)): the selected cells of every row replaced, in place of the row's nested
+    order, by their four children 4 * uniq + j, whose lp_out is NaN until the caller fills it at new_cols; every other cell copied
+    (jf_sky_refine_expand).  sel (C, K): each row ascending and without repeats, as sky_refine_select writes it.  A selected cell that cannot be
+    split (padding, order 29) is kept, followed by three padding cells, and counted in status (JF_STATUS_OUT_OF_RANGE), as is every entry of
+    sel outside [0, M) or not above the one before it (that row's output is then undefined)."""
+    if uniq.dim() != 2 or uniq.dtype != torch.int64 or tuple(lp.shape) != tuple(uniq.shape):
+        raise ValueError("sky_refine_expand: expected int64 uniq (C, M) and lp of the same shape, got %s %s and %s"
+                         % (uniq.dtype, tuple(uniq.shape), tuple(lp.shape)))
+    suf = _suffix(lp)
+    C, M = uniq.shape
+    if sel.dim() != 2 or sel.dtype != torch.int64 or sel.shape[0] != C or sel.shape[1] > M:
+        raise ValueError("sky_refine_expand: sel must be an int64 (C, K) = (%d, K <= %d) tensor, got %s %s" % (C, M, sel.dtype, tuple(sel.shape)))
+    dev = require_device(uniq, lp, sel, status)
+    _sky_refine()
+    uniq, lp, sel = uniq.contiguous(), lp.contiguous(), sel.contiguous()
+    K = sel.shape[1]
+    uniq_out = torch.empty((C, M + 3 * K), dtype=torch.int64, device=uniq.device)
+    lp_out = torch.empty((C, M + 3 * K), dtype=lp.dtype, device=uniq.device)
+    new_cols = torch.empty((C, 4 * K), dtype=torch.int64, device=uniq.device)
+    _launch("jf_sky_refine_expand" + suf, "sky_refine", (_ptr(uniq), _ptr(lp), _ptr(sel), C, M, K, _ptr(uniq_out), _ptr(lp_out), _ptr(new_cols),
+                                                         _ptr(status)), dev)
+    return uniq_out, lp_out, new_cols
+
+
+def sky_refine_entropy(lp, logw, log_norm):
+    """entropy (C,) float64 of the normalised piecewise-constant map of each row: log_norm - sum_m exp(lp + logw - log_norm) * lp, in double and
+    in a fixed order; cells with lp = -inf contribute 0 (jf_sky_refine_entropy).  log_norm (C,) float64 = log sum_m exp(lp + logw)."""
+    if lp.dim() == 2 and (log_norm.dtype != torch.float64 or tuple(log_norm.shape) != (lp.shape[0],)):
+        raise ValueError("sky_refine_entropy: log_norm must be a float64 (C,) = (%d,) tensor, got %s %s"
+                         % (lp.shape[0], log_norm.dtype, tuple(log_norm.shape)))
+    dev, lp, stride, logw, lws = _refine_tile("sky_refine_entropy", lp, logw)
+    C, M = lp.shape
+    require_device(lp, log_norm)
+    log_norm = log_norm.contiguous()
+    out = torch.empty(C, dtype=torch.float64, device=lp.device)
+    _launch("jf_sky_refine_entropy" + _suffix(lp), "sky_refine", (_ptr(lp), stride, _ptr(logw), lws, C, M, _ptr(log_norm), _ptr(out)), dev)
+    return out
 
 
 def _recheck_pair(what, old, new, B, dtype):

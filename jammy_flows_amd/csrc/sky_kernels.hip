@@ -12,14 +12,12 @@
 //
 // The reductions of the header (jf_sky_hpd_*, jf_sky_region_volume_*) are the kernels of hpd_kernels.hip and live there.
 #include "jf_common.h"
-
-#include "../../include/jammy_hip_sky.h"
+#include "jf_sky.h"          // decode_uniq, lower_bound, MAX_ORDER
 
 namespace jf {
 namespace sky {
 
 constexpr int THREADS = 256;
-constexpr int MAX_ORDER = JF_SKY_MAX_ORDER;
 constexpr int64_t NS29 = (int64_t)1 << MAX_ORDER;
 constexpr double PI = 3.141592653589793238462643383279502884, HALF_PI = 0.5 * PI, TWO_OVER_PI = 2.0 / PI, TWO_THIRDS = 2.0 / 3.0;
 
@@ -112,15 +110,6 @@ __global__ void __launch_bounds__(THREADS) vec2pix_kernel(const T* __restrict__ 
     status_add(status, JF_STATUS_NONFINITE, active && bad);
 }
 
-// NUNIQ id -> (order, pixel); false for padding (ids below 4, hence -1) and ids beyond order 29
-__host__ __device__ __forceinline__ bool decode_uniq(int64_t uniq, int& order, int64_t& pix) {
-    if (uniq < 4) return false;
-    const int msb = 63 - __builtin_clzll((unsigned long long)uniq);
-    order = (msb - 2) >> 1;
-    pix = uniq - ((int64_t)4 << (2 * order));
-    return order <= MAX_ORDER;
-}
-
 // centre of nested pixel `pix` at `order`: z = cos(theta), sth = sin(theta) and the azimuth.  The face tables of the paper,
 // jrll = {2,2,2,2, 3,3,3,3, 4,4,4,4} and jpll = {1,3,5,7, 0,2,4,6, 1,3,5,7}, are 2 + face / 4 and 2 (face % 4) + (face / 4 != 1).
 __host__ __device__ __forceinline__ void pix2loc(int order, int64_t pix, double& z, double& sth, double& phi) {
@@ -171,17 +160,6 @@ __global__ void __launch_bounds__(THREADS) cell_centres_kernel(const int64_t* __
         row[0] = (T)atan2(sth, z);
         row[1] = (T)phi;
     }
-}
-
-// first index in [0, n) of the ascending row whose value is >= key (n when there is none)
-__device__ __forceinline__ int64_t lower_bound(const int64_t* __restrict__ row, int64_t n, int64_t key) {
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (row[mid] < key) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
 }
 
 __global__ void __launch_bounds__(THREADS) cell_counts_kernel(const int64_t* __restrict__ sorted_pix, int64_t stride, int64_t G, int64_t S,

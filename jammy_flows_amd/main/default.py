@@ -2541,6 +2541,95 @@ class pdf(nn.Module):
             self._check_sky_mass("sky_mesh", log_norm)
         return ret
 
+    def sky_map_adaptive(self, base_order=4, rounds=7, sub_manifold=None, conditional_input=None, samplesize=100, cells_per_round=None,
+                         labels=None, credible_masses=None, max_tile_elements=2**26, predefined_base=None):
+        """the posterior of an s2 sub-manifold on a density-refined multi-order HEALPix map per conditional input, from the log-prob direction
+        alone (no sampling of the s2 block, no random numbers for sub-manifold 0): the full map of `base_order` is evaluated as sky_map
+        evaluates it, then `rounds` times the K = cells_per_round cells of every row that carry the most probability mass
+        exp(log_prob + log_area) are split into their four children and only those are evaluated -- the adaptive scheme of localisation
+        pipelines (Singer & Price 2016, Phys. Rev. D 93, 024013, section V B).  Every row has M = 12 * 4^base_order + 3 K rounds cells, so
+        the result is a dense tile -> dict of device tensors (C = 1 when unconditional):
+
+            uniq (C, M) int64                NUNIQ ids 4 * 4^order + pix, per row ascending by position in the nested order
+            log_prob (C, M)                  log-density per solid angle at the cell centres (embedding coordinates)
+            log_area (C, M) float64          log solid angle of the cells
+            log_norm (C,) float64            log sum over the row's cells of exp(log_prob + log_area)
+            entropy (C,) float64             log_norm - sum exp(log_prob + log_area - log_norm) * log_prob: the entropy of the normalised
+                                             piecewise-constant map
+            map_uniq (C,) int64, map_direction (C, 3), map_log_prob (C,)          the densest cell (the first among equals)
+          with credible_masses: levels (C, Q), level_masses (C, Q) float64, areas (C, Q) float64 (steradian), as in sky_map
+          with labels (C, 3) or (C, 2): label_cell (C,) int64 (the column), label_log_prob (C,), coverage (C,) float64
+
+        cells_per_round: None = a quarter of the base map, 3 * 4^base_order; with the defaults 3072 + 7 * 3 * 768 = 19 200 cells per row
+        that reach order 11 at the peak.  The selection is a total order (larger mass first, equal masses to the lower column;
+        jf_sky_refine_select), the expansion keeps the nested order (jf_sky_refine_expand): the map is deterministic and a row's cells do
+        not depend on the other rows of the batch.  Behind other blocks (sub_manifold > 0) every evaluation is marginal_log_prob's
+        Monte-Carlo estimate over the same `samplesize` draws -- their base samples are predefined_base, or drawn here once -- so the whole
+        map is one estimator.  With rounds = 0 log_prob carries the bits of sky_map(base_order).  Reductions: the (C, M) tile widened to
+        float64 (exact) with one row of log-areas per conditional input (jf_sky_hpd_* / jf_sky_region_volume / jf_sky_refine_entropy)."""
+        from .. import sky
+        what = "sky_map_adaptive"
+        k, C, qs = self._sky_arguments(what, sub_manifold, conditional_input, labels, credible_masses)
+        if isinstance(base_order, bool) or not isinstance(base_order, int) or not 0 <= base_order <= 13:
+            raise ValueError("%s: base_order must be an integer in [0, 13], got %r" % (what, base_order))
+        if isinstance(rounds, bool) or not isinstance(rounds, int) or rounds < 0:
+            raise ValueError("%s: rounds must be a non-negative integer, got %r" % (what, rounds))
+        if base_order + rounds > sky.MAX_ORDER:
+            raise ValueError("%s: base_order + rounds must not exceed %d (a cell of order %d cannot be split), got %d + %d"
+                             % (what, sky.MAX_ORDER, sky.MAX_ORDER, base_order, rounds))
+        M0 = 12 * 4 ** base_order
+        K = M0 // 4 if cells_per_round is None else cells_per_round
+        if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= M0:
+            raise ValueError("%s: cells_per_round must be an integer in [1, %d] (the cells of the base map), got %r" % (what, M0, cells_per_round))
+        M = M0 + 3 * K * rounds
+        if C * M > 2**31 - 1:
+            raise ValueError("%s: %d conditional inputs x %d cells exceed 2^31 - 1 elements of one tile" % (what, C, M))
+        if isinstance(samplesize, bool) or not isinstance(samplesize, int) or samplesize < 1 or max_tile_elements < 1:
+            raise ValueError("%s: samplesize and max_tile_elements must be positive integers" % what)
+        S = samplesize if k > 0 else 1
+        dt, dev = self.obtain_current_dtype_n_device()
+        first = conditional_input[0] if type(conditional_input) == list else conditional_input
+        if first is not None:
+            dt, dev = first.dtype, first.device
+        _hip.require_device(torch.empty(0, device=dev), labels, predefined_base)
+        with torch.no_grad():
+            z = predefined_base
+            if k > 0 and z is None:                                # one set of draws for the base map and every round
+                z = torch.randn((C * S, self.total_base_dim), dtype=dt, device=dev)
+            kw = dict(conditional_input=conditional_input, samplesize=samplesize, force_embedding_coordinates=True,
+                      max_tile_elements=max_tile_elements, predefined_base=z)
+            base_uniq = sky.uniq_of(base_order, torch.arange(M0, device=dev))
+            lp = self.marginal_log_prob(k, sky.cell_centres(base_uniq, vectors=True, dtype=dt), **kw)
+            uniq = base_uniq[None].expand(C, M0).contiguous()
+            status = _hip.new_status(lp.device) if self.check_status else None
+            for _ in range(rounds):
+                sel = sky.refine_select(lp, sky.cell_log_area(uniq), K, status)
+                uniq, lp, new_cols = sky.refine_expand(uniq, lp, sel, status)
+                centres = sky.cell_centres(uniq.gather(1, new_cols), vectors=True, dtype=dt)          # (C, 4 K, 3)
+                lp.scatter_(1, new_cols, self.marginal_log_prob(k, centres, **kw))
+            if labels is not None:
+                label_pix = sky.vec2pix(sky.MAX_ORDER, labels.to(dt), status)
+            self._report_status(status)
+            log_area = sky.cell_log_area(uniq)
+            tile = lp.double()
+            log_norm, max_lp, argmax = _hip.sky_hpd_stats(tile, log_area)
+            map_uniq = uniq.gather(1, argmax.clamp(min=0)[:, None])[:, 0]
+            ret = {"uniq": uniq, "log_prob": lp, "log_area": log_area, "log_norm": log_norm, "entropy": sky.map_entropy(lp, log_area, log_norm),
+                   "map_uniq": map_uniq, "map_direction": sky.cell_centres(map_uniq, vectors=True, dtype=dt), "map_log_prob": max_lp.to(lp.dtype)}
+            if qs is not None:
+                levels, ret["level_masses"] = _hip.sky_hpd_levels(tile, qs, log_norm, log_area)
+                ret["levels"] = levels.to(lp.dtype)
+                ret["areas"] = _hip.sky_region_volume(tile, levels, log_area)
+            if labels is not None:
+                offsets = torch.arange(C + 1, device=lp.device) * M
+                cell = sky.locate(sky.cell_start(uniq).reshape(-1), offsets, label_pix[:, None])[:, 0]
+                col = torch.where(cell >= 0, cell - offsets[:-1], cell)
+                label_lp = tile.gather(1, col.clamp(min=0)[:, None])
+                ret.update(label_cell=col, label_log_prob=label_lp[:, 0].to(lp.dtype),
+                           coverage=_hip.sky_hpd_mass(tile, label_lp, log_norm, log_area)[:, 0])
+            self._check_sky_mass(what, log_norm)
+        return ret
+
     def _first_marginal_logp(self, x0, data_summary):
         """log-pdf of the first sub-manifold's marginal at x0 (embedding coordinates): block 0 depends on the conditional input alone, so the
         later blocks are filled with ones and only block 0's base log-prob and log-det are kept (as the marginal entropies do)."""

@@ -122,6 +122,30 @@ def locate(starts, offsets, pix):
     return out
 
 
+def refine_select(lp, log_area, K, status=None):
+    """the K most massive cells of every row -> sel (C, K) int64, ascending columns.  lp (C, M) log-densities (float32 or float64) and
+    log_area float64 (M,), (C, M) or None, on the device; the key of a cell is (double)lp + log_area, the log of its probability mass.  The
+    order is total -- a larger key wins, equal keys go to the lower column, NaN ranks as -inf and is counted in `status` under
+    JF_STATUS_NONFINITE, -0.0 counts as +0.0 -- so the result is unique and a row's does not depend on the other rows
+    (jf_sky_refine_select)."""
+    return _hip.sky_refine_select(lp, log_area, K, status)
+
+
+def refine_expand(uniq, lp, sel, status=None):
+    """split the selected cells of every row into their four children -> (uniq_out (C, M + 3 K), lp_out (C, M + 3 K), new_cols (C, 4 K)).
+    uniq (C, M) int64 NUNIQ ids in nested order, lp (C, M), sel (C, K) as refine_select returns it.  Cell m moves to column m + 3 * (number
+    of selected columns below m); a selected cell's children 4 * uniq + j take its column and the three after it, lp_out is NaN there and
+    new_cols names those columns, child by child.  The nested order of a row is preserved (jf_sky_refine_expand)."""
+    return _hip.sky_refine_expand(uniq, lp, sel, status)
+
+
+def map_entropy(lp, log_area, log_norm):
+    """entropy (C,) float64 of the normalised piecewise-constant maps lp (C, M) with the cells' log_area (float64 (M,), (C, M) or None) and
+    log_norm (C,) float64 = log sum exp(lp + log_area): log_norm - sum exp(lp + log_area - log_norm) * lp -- what the reference's
+    s2_entropy_scanning sums over a flat map (jf_sky_refine_entropy)."""
+    return _hip.sky_refine_entropy(lp, log_area, log_norm)
+
+
 class Mesh:
     """C multi-order meshes in CSR form: row c's leaves are uniq[offsets[c]:offsets[c + 1]], ascending by their order-29 range start, and
     partition the sphere; counts holds the samples each leaf received."""
