@@ -325,6 +325,20 @@ JF_SKY_REFINE_ABI = 1
 SKY_REFINE_CHUNK = 256           # JF_SKY_REFINE_CHUNK: columns per step of a row's walk (csrc/sky_refine_kernels.hip)
 _sky_refine_bound = False
 
+# name -> (argtypes, restype): segmented order statistics, include/jammy_hip_order.h (a sixth header with an ABI number of its own).  Bound on
+# first use by _order().
+_SIGNATURES_ORDER = {"jf_order_abi_version": ([], ctypes.c_int)}
+for _d in ("_f32", "_f64"):
+    #                                             x  stride G     S     W   sorted n_valid status
+    _SIGNATURES_ORDER["jf_order_sort" + _d] = ([_P, _I64, _I64, _I64, _I64, _P, _P, _P, _P], ctypes.c_int)
+    #                                               sorted n_valid R   S   probs Q    out status
+    _SIGNATURES_ORDER["jf_order_quantiles" + _d] = ([_P, _P, _I64, _I64, _P, _I64, _P, _P, _P], ctypes.c_int)
+    #                                              sorted n_valid R   S  counts T     period           low high width start status
+    _SIGNATURES_ORDER["jf_order_shortest" + _d] = ([_P, _P, _I64, _I64, _P, _I64, ctypes.c_double, _P, _P, _P, _P, _P, _P], ctypes.c_int)
+JF_ORDER_ABI = 1
+ORDER_MAX_S = 16384              # JF_ORDER_MAX_S: entries of a segment, held in one workgroup's LDS (csrc/order_kernels.hip)
+_order_bound = False
+
 
 def exported_symbols():
     """all symbols include/jammy_hip.h declares (used by the CPU-side ABI test)."""
@@ -418,6 +432,16 @@ def _sky_refine():
         return lib()
     l = _bind_header(_SIGNATURES_SKY_REFINE, "jammy_hip_sky_refine.h", "jf_sky_refine_abi_version", JF_SKY_REFINE_ABI, "sky refine")
     _sky_refine_bound = True
+    return l
+
+
+def _order():
+    """the same for include/jammy_hip_order.h"""
+    global _order_bound
+    if _order_bound:
+        return lib()
+    l = _bind_header(_SIGNATURES_ORDER, "jammy_hip_order.h", "jf_order_abi_version", JF_ORDER_ABI, "order")
+    _order_bound = True
     return l
 
 
@@ -2045,6 +2069,81 @@ def sky_refine_entropy(lp, logw, log_norm):
     out = torch.empty(C, dtype=torch.float64, device=lp.device)
     _launch("jf_sky_refine_entropy" + _suffix(lp), "sky_refine", (_ptr(lp), stride, _ptr(logw), lws, C, M, _ptr(log_norm), _ptr(out)), dev)
     return out
+
+
+def order_sort(x, S, status=None):
+    """(sorted (G, W, S), n_valid (G, W) int64): every column of every segment of S consecutive rows of x (G * S, W) in ascending order -- the
+    total order of include/jammy_hip_order.h: -inf first, -0.0 before +0.0, every NaN after +inf (counted in status under JF_STATUS_NONFINITE)
+    -- and the number of entries that are not NaN.  The values are the input's, bit for bit (jf_order_sort).  x may be a column slice of a
+    wider row-major tensor: its row stride is passed on."""
+    if isinstance(S, bool) or not isinstance(S, int) or S < 1:
+        raise ValueError("order_sort: the segment length S must be a positive integer, got %r" % (S,))
+    if x.dim() != 2 or x.shape[0] % S != 0:
+        raise ValueError("order_sort: expected a (G * S, W) tile with S = %d, got shape %s" % (S, tuple(x.shape)))
+    suf = _suffix(x)
+    dev = require_device(x, status)
+    _order()
+    x = _rowmajor(x)
+    G, W = x.shape[0] // S, x.shape[1]
+    stride = x.stride(0) if x.shape[0] > 1 else max(W, 1)
+    out = torch.empty((G, W, S), dtype=x.dtype, device=x.device)
+    n_valid = torch.empty((G, W), dtype=torch.int64, device=x.device)
+    _launch("jf_order_sort" + suf, "order", (_ptr(x), stride, G, S, W, _ptr(out), _ptr(n_valid), _ptr(status)), dev)
+    return out, n_valid
+
+
+def _order_rows(what, rows, n_valid):
+    """the arguments quantiles and shortest share: rows (..., S) ascending, n_valid int64 of the leading shape or None -> leading shape"""
+    if rows.dim() < 1:
+        raise ValueError("%s: expected sorted rows (..., S), got shape %s" % (what, tuple(rows.shape)))
+    _suffix(rows)
+    lead = tuple(rows.shape[:-1])
+    if n_valid is not None and (n_valid.dtype != torch.int64 or tuple(n_valid.shape) != lead):
+        raise ValueError("%s: n_valid must be an int64 %s tensor, got %s %s" % (what, lead, n_valid.dtype, tuple(n_valid.shape)))
+    return lead
+
+
+def order_quantiles(rows, probs, n_valid=None, status=None):
+    """out (..., Q): the quantiles `probs` (Q,) float64 on the device of the first n_valid entries of every ascending row of rows (..., S), by
+    linear interpolation between order statistics in double, rounded once; an order statistic itself where the rank is whole.  A row without
+    entries gives NaN; a probability outside [0, 1] gives NaN and is counted in status under JF_STATUS_OUT_OF_RANGE (jf_order_quantiles)."""
+    lead = _order_rows("order_quantiles", rows, n_valid)
+    if probs.dim() != 1 or probs.dtype != torch.float64:
+        raise ValueError("order_quantiles: probs must be a float64 (Q,) tensor, got %s %s" % (probs.dtype, tuple(probs.shape)))
+    dev = require_device(rows, probs, n_valid, status)
+    _order()
+    S, Q = rows.shape[-1], probs.shape[0]
+    rows, probs = rows.contiguous(), probs.contiguous()
+    n_valid = None if n_valid is None else n_valid.contiguous()
+    R = rows.numel() // S if S else 0
+    out = torch.empty(lead + (Q,), dtype=rows.dtype, device=rows.device)
+    _launch("jf_order_quantiles" + _suffix(rows), "order", (_ptr(rows), _ptr(n_valid), R, S, _ptr(probs), Q, _ptr(out), _ptr(status)), dev)
+    return out
+
+
+def order_shortest(rows, counts, period=None, n_valid=None, status=None):
+    """(low, high, width, start), each (..., T): for every ascending row of rows (..., S) and every k = clamp(counts[t], 1, n_valid) the window
+    of k consecutive order statistics of least width -- with a period > 0 on the circle of that circumference, where a window may run over the
+    row's end and high < low then marks an arc across the seam.  low, high: sample values; width: float64; start: int64, the index of low.
+    Equal widths go to the lowest start; a row without entries gives NaN and -1 (jf_order_shortest).  counts: int64 (T,) on the device."""
+    lead = _order_rows("order_shortest", rows, n_valid)
+    if counts.dim() != 1 or counts.dtype != torch.int64:
+        raise ValueError("order_shortest: counts must be an int64 (T,) tensor, got %s %s" % (counts.dtype, tuple(counts.shape)))
+    if period is not None and (isinstance(period, bool) or not isinstance(period, (int, float)) or not 0.0 < period < float("inf")):
+        raise ValueError("order_shortest: period must be None (a linear coordinate) or a positive finite number, got %r" % (period,))
+    dev = require_device(rows, counts, n_valid, status)
+    _order()
+    S, T = rows.shape[-1], counts.shape[0]
+    rows, counts = rows.contiguous(), counts.contiguous()
+    n_valid = None if n_valid is None else n_valid.contiguous()
+    R = rows.numel() // S if S else 0
+    low = torch.empty(lead + (T,), dtype=rows.dtype, device=rows.device)
+    high = torch.empty_like(low)
+    width = torch.empty(lead + (T,), dtype=torch.float64, device=rows.device)
+    start = torch.empty(lead + (T,), dtype=torch.int64, device=rows.device)
+    _launch("jf_order_shortest" + _suffix(rows), "order", (_ptr(rows), _ptr(n_valid), R, S, _ptr(counts), T, 0.0 if period is None else float(period),
+                                                           _ptr(low), _ptr(high), _ptr(width), _ptr(start), _ptr(status)), dev)
+    return low, high, width, start
 
 
 def _recheck_pair(what, old, new, B, dtype):

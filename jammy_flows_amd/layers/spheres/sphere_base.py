@@ -6,6 +6,8 @@ all of it in ONE HIP kernel on intrinsic coordinates (``_fused``); third-party s
 ``_flow_mapping`` / ``_inv_flow_mapping`` get the rotation and the chart from the 'c' kernels (``inv_flow_mapping`` below).
 ``num_householder_iter`` doubles as the kernels' rotation code: >= 0 Householder reflections, -1 / -2 / -3 = angles / xyz / quaternion.
 """
+import math
+
 import torch
 from torch import nn
 
@@ -184,6 +186,12 @@ class sphere_base(layer_base.layer_base):
 
     def _embedding_conditional_return_num(self):
         return self.dimension + 1
+
+    def intrinsic_periods(self):
+        """per intrinsic coordinate, in column order: its period where it is circular, else None.  S1: the angle in [0, 2 pi).  S2:
+        (theta, phi) = (zenith in [0, pi], azimuth in [0, 2 pi)), as eucl_to_spherical_embedding returns them (sphere_base.py:248-300): the
+        zenith is an interval, the azimuth closes on itself."""
+        return (2.0 * math.pi,) if self.dimension == 1 else (None, 2.0 * math.pi)
 
     def transform_target_space(self, x, log_det=0.0, transform_from="default", transform_to="embedding"):
         """default / intrinsic / embedding coordinates (sphere_base.py:796-841)."""

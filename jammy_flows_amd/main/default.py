@@ -24,6 +24,7 @@ from ..amortizable_mlp import AmortizableMLP
 from ..extra_functions import list_from_str, recheck_sampling
 from ..flow_options import canonical, check_flow_option, layer_class, obtain_default_options, opts_dict
 from ..layers.euclidean import gaussianization_flow as gfl
+from ..layers.spheres import sphere_base
 
 
 # float64 amortisation MLPs with a wide output: "i8x6" / "i8x5" = second product as int8 digit-slice products (operands kept to 2^-41 / 2^-34,
@@ -2078,6 +2079,98 @@ class pdf(nn.Module):
         finally:
             for i, f in enumerate(previous_flags):
                 self.set_embedding_flags(f, sub_pdf_index=i)
+        return ret
+
+    def _intrinsic_periods(self):
+        """per intrinsic target column, in column order: the period of a circular coordinate (the s1 angle, the s2 azimuth) or None for a
+        linear one (e and i coordinates, the s2 zenith)"""
+        periods = []
+        for block in self.layer_list:
+            last = block[-1]
+            if isinstance(last, sphere_base.sphere_base):
+                periods += list(last.intrinsic_periods())
+            else:
+                periods += [None] * last.get_layer_intrinsic_target_dimension()
+        assert len(periods) == self.total_target_dim_intrinsic
+        return periods
+
+    def marginal_quantiles(self, probs=(0.16, 0.5, 0.84), credible_masses=(0.68, 0.9), conditional_input=None, samplesize=1000,
+                           sub_manifolds=None, predefined_base=None, seed=None, return_samples=False, dtype=None, device=None):
+        """Order statistics of every one-dimensional marginal, per conditional input, from `samplesize` joint samples in intrinsic coordinates:
+        what numpy.percentile on host copies of sample() output gives, computed on the device (jammy_flows_amd.order) -> dict of device
+        tensors, for every sub-manifold k of `sub_manifolds` (None: all) with its d_k intrinsic coordinates (C = 1 when unconditional):
+
+            quantiles_k (C, Q, d_k)            the quantiles `probs` (numpy's linear rule); NaN in circular columns, which have no least value
+            interval_low_k, interval_high_k (C, T, d_k)     the shortest interval that holds ceil(mass * samplesize) samples, for every mass
+                                               of `credible_masses`: sample values; on a circular coordinate the shortest arc, and
+                                               high < low marks an arc across the seam of the coordinate's range
+            interval_width_k (C, T, d_k) float64           its width, modulo the period on a circular coordinate
+            circular_k                         a tuple of d_k bools: the s1 angle and the s2 azimuth are circular (period 2 pi); e and i
+                                               coordinates and the s2 zenith are linear
+            samples_k (C, samplesize, d_k)     with return_samples
+
+        One sort of the whole (C * samplesize, D) sample tile, one quantile launch and one interval launch on the linear columns, one
+        interval launch on the circular ones; the status words are read back once.  The order is total (include/jammy_hip_order.h) and a
+        conditional input's results do not depend on the others in the batch.  `predefined_base` injects the standard-normal base
+        samples, `seed` draws them as sample(seed=...) does.  The pdf's embedding flags are left as they are: the samples are those of
+        _obtain_sample(force_intrinsic_coordinates=True)."""
+        from .. import order
+        S = samplesize
+        if isinstance(S, bool) or not isinstance(S, int) or not 1 <= S <= order.MAX_SEGMENT:
+            raise ValueError("marginal_quantiles: samplesize must be an integer in [1, %d] (a segment is sorted in one workgroup's LDS), got %r"
+                             % (order.MAX_SEGMENT, S))
+        ps = [float(v) for v in (probs.tolist() if hasattr(probs, "tolist") else probs)]
+        if not all(0.0 <= v <= 1.0 for v in ps):
+            raise ValueError("marginal_quantiles: probs must be numbers in [0, 1], got %s" % (ps,))
+        ms = [float(v) for v in (credible_masses.tolist() if hasattr(credible_masses, "tolist") else credible_masses)]
+        if not all(0.0 < v <= 1.0 for v in ms):
+            raise ValueError("marginal_quantiles: credible_masses must be numbers in (0, 1], got %s" % (ms,))
+        nsub = len(self.pdf_defs_list)
+        blocks = list(range(nsub)) if sub_manifolds is None else list(sub_manifolds)
+        for k in blocks:
+            if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k < nsub:
+                raise ValueError("marginal_quantiles: sub_manifolds must be indices in [0, %d), got %r" % (nsub, k))
+        counts = [order.count_for_mass(m, S) for m in ms]
+        periods = self._intrinsic_periods()
+        cols = [c for k in blocks for c in range(*self.target_dim_indices_intrinsic[k])]
+        lin = [c for c in cols if periods[c] is None]
+        circ = [c for c in cols if periods[c] is not None]
+        assert all(periods[c] == 2.0 * numpy.pi for c in circ)
+        dt, dev, batch, data_summary = self._repeat_conditional(conditional_input, S, dtype, device)
+        ret = {}
+        with torch.no_grad():
+            samples = self._obtain_sample(conditional_input=data_summary, predefined_target_input=predefined_base, samplesize=S, seed=seed,
+                                          force_intrinsic_coordinates=True, dtype=dt, device=dev)[0]
+            D = self.total_target_dim_intrinsic
+            assert samples.shape == (batch * S, D)
+            status = _hip.new_status(samples.device) if self.check_status else None
+            rows, n_valid = order.sort_segments(samples, S, status)                    # (C, D, S), (C, D)
+            Q, T = len(ps), len(ms)
+            quant = torch.full((batch, D, Q), float("nan"), dtype=samples.dtype, device=samples.device)
+            low = torch.empty((batch, D, T), dtype=samples.dtype, device=samples.device)
+            high = torch.empty_like(low)
+            width = torch.empty((batch, D, T), dtype=torch.float64, device=samples.device)
+            d_counts = torch.tensor(counts, dtype=torch.int64, device=samples.device)
+            d_probs = torch.tensor(ps, dtype=torch.float64, device=samples.device)
+            for group, period in ((lin, None), (circ, 2.0 * numpy.pi)):
+                if not group:
+                    continue
+                whole = group == list(range(D))
+                sub, nv = (rows, n_valid) if whole else (rows[:, group], n_valid[:, group])
+                if period is None and Q > 0:
+                    quant[:, group] = order.quantiles(sub, d_probs, nv, status)
+                if T > 0:
+                    low[:, group], high[:, group], width[:, group], _ = order.shortest_intervals(sub, d_counts, period, nv, status)
+            for k in blocks:
+                a, b = self.target_dim_indices_intrinsic[k]
+                ret["quantiles_%d" % k] = quant[:, a:b].transpose(1, 2).contiguous()
+                ret["interval_low_%d" % k] = low[:, a:b].transpose(1, 2).contiguous()
+                ret["interval_high_%d" % k] = high[:, a:b].transpose(1, 2).contiguous()
+                ret["interval_width_%d" % k] = width[:, a:b].transpose(1, 2).contiguous()
+                ret["circular_%d" % k] = tuple(periods[c] is not None for c in range(a, b))
+                if return_samples:
+                    ret["samples_%d" % k] = samples[:, a:b].reshape(batch, S, b - a)
+            self._report_status(status)
         return ret
 
     # =========================================================================================== densities on product grids / marginals
