@@ -339,6 +339,23 @@ JF_ORDER_ABI = 1
 ORDER_MAX_S = 16384              # JF_ORDER_MAX_S: entries of a segment, held in one workgroup's LDS (csrc/order_kernels.hip)
 _order_bound = False
 
+# name -> (argtypes, restype): the zlp-Kent fit on S2, include/jammy_hip_kent.h (a seventh header with an ABI number of its own).  Bound on
+# first use by _kent().
+_F64 = ctypes.c_double
+_SIGNATURES_KENT = {"jf_kent_abi_version": ([], ctypes.c_int)}
+for _d in ("_f32", "_f64"):
+    #                                          x  stride G     S    mu kappa_vmf max_iter tols and steps  3 gammas, 5 doubles, 2 ints, status
+    _SIGNATURES_KENT["jf_kent_fit" + _d] = ([_P, _I64, _I64, _I64, _P, _P, _I32, _F64, _F64, _F64, _F64] + [_P] * 12, ctypes.c_int)
+    #                                             targets G   T    gamma1..3, kappa, u  out stream
+    _SIGNATURES_KENT["jf_kent_log_prob" + _d] = ([_P, _I64, _I64, _P, _P, _P, _P, _P, _P, _P], ctypes.c_int)
+#                                           base G     M    gamma1..3, kappa, u  out stream
+_SIGNATURES_KENT["jf_kent_sample_f64"] = ([_P, _I64, _I64, _P, _P, _P, _P, _P, _P, _P], ctypes.c_int)
+#                                             base G     M    gamma1..3, kappa, u   logp T  coverage stream
+_SIGNATURES_KENT["jf_kent_coverage_f64"] = ([_P, _I64, _I64, _P, _P, _P, _P, _P, _P, _I64, _P, _P], ctypes.c_int)
+JF_KENT_ABI = 1
+KENT_MAX_S = 4096                # JF_KENT_MAX_S: samples of a segment, held rotated in one workgroup's LDS (csrc/kent_kernels.hip)
+_kent_bound = False
+
 
 def exported_symbols():
     """all symbols include/jammy_hip.h declares (used by the CPU-side ABI test)."""
@@ -442,6 +459,16 @@ def _order():
         return lib()
     l = _bind_header(_SIGNATURES_ORDER, "jammy_hip_order.h", "jf_order_abi_version", JF_ORDER_ABI, "order")
     _order_bound = True
+    return l
+
+
+def _kent():
+    """the same for include/jammy_hip_kent.h"""
+    global _kent_bound
+    if _kent_bound:
+        return lib()
+    l = _bind_header(_SIGNATURES_KENT, "jammy_hip_kent.h", "jf_kent_abi_version", JF_KENT_ABI, "kent")
+    _kent_bound = True
     return l
 
 
@@ -2144,6 +2171,112 @@ def order_shortest(rows, counts, period=None, n_valid=None, status=None):
     _launch("jf_order_shortest" + _suffix(rows), "order", (_ptr(rows), _ptr(n_valid), R, S, _ptr(counts), T, 0.0 if period is None else float(period),
                                                            _ptr(low), _ptr(high), _ptr(width), _ptr(start), _ptr(status)), dev)
     return low, high, width, start
+
+
+# the outputs of jf_kent_fit, in the order of its arguments
+KENT_FIT_KEYS = ("gamma1", "gamma2", "gamma3", "kappa", "u", "safe_log_u", "u_log_upper_bound", "loglik", "converged", "num_iter")
+
+
+def kent_fit(x, S, mu=None, kappa_vmf=None, max_iter=300, grad_tol=1e-5, rel_obj_tol=1e-8, fd_eps=1e-4, armijo_c1=1e-4, status=None):
+    """the zlp-Kent fit of every segment of S consecutive unit vectors of x (G * S, 3), float32 or float64, in ONE launch -> dict of float64 /
+    int32 device tensors with a leading G: gamma1, gamma2, gamma3 (G, 3), kappa, u, safe_log_u, u_log_upper_bound, loglik, converged, num_iter
+    (jf_kent_fit, include/jammy_hip_kent.h).  mu (G, 3) / kappa_vmf (G,): the start, None = from the segment's mean vector.  x may be a
+    column slice of a wider row-major tensor: its row stride is passed on."""
+    if isinstance(S, bool) or not isinstance(S, int) or not 2 <= S <= KENT_MAX_S:
+        raise ValueError("kent_fit: the segment length S must be an integer in [2, %d] (a segment is held in one workgroup's LDS), got %r"
+                         % (KENT_MAX_S, S))
+    if x.dim() != 2 or x.shape[1] != 3 or x.shape[0] % S != 0:
+        raise ValueError("kent_fit: expected a (G * S, 3) tile with S = %d, got shape %s" % (S, tuple(x.shape)))
+    if isinstance(max_iter, bool) or not isinstance(max_iter, int) or max_iter < 0:
+        raise ValueError("kent_fit: max_iter must be a non-negative integer, got %r" % (max_iter,))
+    if not float(fd_eps) > 0.0:
+        raise ValueError("kent_fit: fd_eps must be positive, got %r" % (fd_eps,))
+    suf = _suffix(x)
+    G = x.shape[0] // S
+    for name, t, shape in (("mu", mu, (G, 3)), ("kappa_vmf", kappa_vmf, (G,))):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError("kent_fit: %s must have shape %s, got %s" % (name, shape, tuple(t.shape)))
+    dev = require_device(x, mu, kappa_vmf, status)
+    _kent()
+    x = _rowmajor(x)
+    stride = x.stride(0) if x.shape[0] > 1 else 3
+    mu = None if mu is None else mu.to(torch.float64).contiguous()
+    kappa_vmf = None if kappa_vmf is None else kappa_vmf.to(torch.float64).contiguous()
+    f64 = dict(dtype=torch.float64, device=x.device)
+    out = {k: torch.empty((G, 3), **f64) for k in ("gamma1", "gamma2", "gamma3")}
+    out.update({k: torch.empty((G,), **f64) for k in ("kappa", "u", "safe_log_u", "u_log_upper_bound", "loglik")})
+    out.update({k: torch.empty((G,), dtype=torch.int32, device=x.device) for k in ("converged", "num_iter")})
+    _launch("jf_kent_fit" + suf, "kent", (_ptr(x), stride, G, S, _ptr(mu), _ptr(kappa_vmf), max_iter, float(grad_tol), float(rel_obj_tol),
+                                          float(fd_eps), float(armijo_c1)) + tuple(_ptr(out[k]) for k in KENT_FIT_KEYS) + (_ptr(status),), dev)
+    return out
+
+
+def _kent_fit_args(what, fit):
+    """the five arrays of a fit the density and the sampler read -> (G, [gamma1, gamma2, gamma3, kappa, u] contiguous float64)"""
+    try:
+        parts = [fit[k] for k in ("gamma1", "gamma2", "gamma3", "kappa", "u")]
+    except (KeyError, TypeError, IndexError):
+        raise ValueError("%s: fit must be a dict with gamma1, gamma2, gamma3 (G, 3) and kappa, u (G,), as kent.fit returns" % what)
+    G = parts[3].shape[0] if parts[3].dim() == 1 else -1
+    for k, t, shape in zip(("gamma1", "gamma2", "gamma3", "kappa", "u"), parts, ((G, 3),) * 3 + ((G,),) * 2):
+        if G < 0 or tuple(t.shape) != shape or t.dtype != torch.float64:
+            raise ValueError("%s: fit[%r] must be a float64 %s tensor, got %s %s" % (what, k, "(G, 3)" if len(shape) == 2 else "(G,)", t.dtype,
+                                                                                   tuple(t.shape)))
+    return G, [t.contiguous() for t in parts]
+
+
+def kent_log_prob(fit, targets):
+    """(G, T) float64: the log-density of targets (G, T, 3), float32 or float64 (any length: they are normalised), under the G fits
+    (jf_kent_log_prob)"""
+    G, parts = _kent_fit_args("kent_log_prob", fit)
+    if targets.dim() != 3 or targets.shape[0] != G or targets.shape[2] != 3:
+        raise ValueError("kent_log_prob: targets must be (G, T, 3) with G = %d, got shape %s" % (G, tuple(targets.shape)))
+    suf = _suffix(targets)
+    dev = require_device(targets, *parts)
+    _kent()
+    targets = targets.contiguous()
+    T = targets.shape[1]
+    out = torch.empty((G, T), dtype=torch.float64, device=targets.device)
+    _launch("jf_kent_log_prob" + suf, "kent", (_ptr(targets), G, T) + tuple(_ptr(t) for t in parts) + (_ptr(out),), dev)
+    return out
+
+
+def _kent_base(what, base, G):
+    if base.dim() != 3 or base.shape[0] != G or base.shape[2] != 3 or base.dtype != torch.float64:
+        raise ValueError("%s: base must be a float64 (G, M, 3) tensor of standard normals with G = %d, got %s %s"
+                         % (what, G, base.dtype, tuple(base.shape)))
+    return base.contiguous()
+
+
+def kent_sample(fit, base):
+    """(G, M, 3) float64: the draws of the G fits that the standard-normal triples base (G, M, 3) map to (jf_kent_sample_f64)"""
+    G, parts = _kent_fit_args("kent_sample", fit)
+    base = _kent_base("kent_sample", base, G)
+    dev = require_device(base, *parts)
+    _kent()
+    out = torch.empty_like(base)
+    _launch("jf_kent_sample_f64", "kent", (_ptr(base), G, base.shape[1]) + tuple(_ptr(t) for t in parts) + (_ptr(out),), dev)
+    return out
+
+
+def kent_coverage(fit, base, target_logp):
+    """(G, T) float64: the share of the M draws of base (G, M, 3) that are at least as dense under their fit as target_logp (G, T); the draws
+    are made and scored inside the kernel (jf_kent_coverage_f64)"""
+    G, parts = _kent_fit_args("kent_coverage", fit)
+    base = _kent_base("kent_coverage", base, G)
+    if target_logp.dim() != 2 or target_logp.shape[0] != G or target_logp.dtype != torch.float64:
+        raise ValueError("kent_coverage: target_logp must be a float64 (G, T) tensor with G = %d, got %s %s"
+                         % (G, target_logp.dtype, tuple(target_logp.shape)))
+    if base.shape[1] < 1:
+        raise ValueError("kent_coverage: needs at least one draw per fit, got base of shape %s" % (tuple(base.shape),))
+    dev = require_device(base, target_logp, *parts)
+    _kent()
+    target_logp = target_logp.contiguous()
+    T = target_logp.shape[1]
+    out = torch.empty((G, T), dtype=torch.float64, device=base.device)
+    _launch("jf_kent_coverage_f64", "kent", (_ptr(base), G, base.shape[1]) + tuple(_ptr(t) for t in parts) + (_ptr(target_logp), T, _ptr(out)),
+            dev)
+    return out
 
 
 def _recheck_pair(what, old, new, B, dtype):

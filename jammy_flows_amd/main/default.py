@@ -437,6 +437,8 @@ class pdf(nn.Module):
         self.lowrank_chain_training = os.environ.get("JF_LOWRANK_CHAIN_TRAINING", "1") != "0"
         self.use_step_plans = os.environ.get("JF_STEP_PLANS", "0") == "1"      # forward() through recorded step plans (planned_forward)
         self.last_recheck = None         # what the last checked sampling call redrew (extra_functions.recheck_sampling)
+        # marginal_moments also returns the reference's zlp_kent_* keys of every s2 sub-manifold (jammy_flows_amd.kent: one launch more)
+        self.marginal_moments_zlp_kent = False
         # float32 log-prob steps of up to merge_max_rows rows that start with an unconditional broadcast g chain and a one-launch `f` block issue
         # the two as ONE launch (csrc/merged_kernels.hip: they overlap each other's latency -- 0.055 -> 0.037 ms at 2^17 rows, 0.228 -> 0.210 at
         # 2^20); 0 = never
@@ -2015,8 +2017,13 @@ class pdf(nn.Module):
         cross_entropy_k - entropy_k, and for k = 0 reverse_cross_entropy_0 / kl_diff_approx_exact_0 from draws of the fit.  Sampling, the
         per-group sums (jf_segment_moments) and the entropies run on the device; every returned array is copied to the host once.
         `predefined_base` injects the standard-normal base samples (tests).
-        Not provided: s2_entropy_scanning (needs healpy: NotImplementedError) and the reference's zlp_kent_* keys (its Kent fit is an
-        optimiser of its own, outside this method).  S1 uses log c = -log(2 pi I0(kappa)) (the reference's S1 branch never assigns it)."""
+        With self.marginal_moments_zlp_kent = True also, for every s2 sub-manifold, the reference's zlp_kent_gamma1_k, zlp_kent_gamma2_k, zlp_kent_gamma3_k (batch, 3),
+        zlp_kent_kappa_k and zlp_kent_u_k (batch,), float64: the zlp-Kent fit of its samples started from mean_k and varlike_k as the
+        reference starts it, one launch for all conditional inputs (jammy_flows_amd.kent; pdf.s2_kent_fit adds the fit's log-density and
+        coverage at labels).  The reference always returns these keys; here they are off by default, and the switch is an attribute of
+        the pdf, like check_status, so that the method's keywords stay the reference's.
+        Not provided: s2_entropy_scanning (needs healpy: NotImplementedError).  S1 uses log c = -log(2 pi I0(kappa)) (the reference's S1
+        branch never assigns it)."""
         if failsafe_crosscheck_tolerance:
             raise NotImplementedError("failsafe_crosscheck_tolerance (recheck_sampling) is outside the MI355X hot path")
         if s2_entropy_scanning:
@@ -2060,6 +2067,11 @@ class pdf(nn.Module):
                                                                                kl, kl and k == 0, return_samples)
                         for key, v in sphere.items():
                             ret[key % k] = v
+                        if self.marginal_moments_zlp_kent and pdef == "s2":
+                            from .. import kent
+                            kfit = kent.fit(sub, S, mu=mean, kappa_vmf=varlike.reshape(batch))
+                            for key in ("gamma1", "gamma2", "gamma3", "kappa", "u"):
+                                ret["zlp_kent_%s_%d" % (key, k)] = _host(kfit[key])
                     ret["mean_%d" % k] = _host(mean)
                     ret["argmax_%d" % k] = _host(arg_max)
                     ret["varlike_%d" % k] = _host(varlike)
@@ -2172,6 +2184,58 @@ class pdf(nn.Module):
                     ret["samples_%d" % k] = samples[:, a:b].reshape(batch, S, b - a)
             self._report_status(status)
         return ret
+
+    def s2_kent_fit(self, sub_manifold=None, conditional_input=None, samplesize=1000, labels=None, coverage_samples=10000, seed=None,
+                    predefined_base=None, dtype=None, device=None):
+        """The zlp-Kent approximation (arXiv 2510.04762) of the marginal of an s2 sub-manifold, per conditional input, from `samplesize` joint
+        samples in embedding coordinates (drawn as marginal_moments draws them): the error ellipse of a direction posterior and, with
+        labels, its per-event coverage, computed on the device (jammy_flows_amd.kent) -> dict of host arrays (C = 1 when unconditional):
+
+            gamma1, gamma2, gamma3 (C, 3)      the mean direction (the samples' resultant direction), the major and the minor axis of the
+                                               ellipse; (gamma2, gamma3) are defined up to a joint sign
+            kappa, u (C,)                      concentration and ellipticity, u < sqrt(1 + kappa / 3)
+            loglik (C,)                        the log-likelihood of the samples under the fit
+            converged, num_iter (C,)           per conditional input (the reference counts iterations for the whole batch only)
+          with labels (C, 3) vectors or (C, 2) angles (zenith, azimuth):
+            label_log_prob (C,)                the fit's log-density per solid angle at the label
+            label_coverage (C,)                the mass of the fit's highest-density region through the label, from `coverage_samples`
+                                               draws of the fit: torch's generator on the device seeded with `seed` (None: 0), not the
+                                               reference's numpy draws, so it agrees with zlp_kent_coverage to sampling noise
+
+        sub_manifold: the index of the s2 block; None = the pdf's only one.  The fit starts from the resultant direction and the isotropic
+        concentration of its length (marginal_moments with marginal_moments_zlp_kent starts from its own von-Mises-Fisher kappa instead).  One launch
+        fits all conditional inputs, one scores and one covers the labels; everything is copied to the host once, at the end.
+        `predefined_base` injects the standard-normal base samples, `seed` also draws them as sample(seed=...) does."""
+        from .. import kent
+        k, C, _ = self._sky_arguments("s2_kent_fit", sub_manifold, conditional_input, labels, None)
+        S = samplesize
+        if isinstance(S, bool) or not isinstance(S, int) or not 2 <= S <= kent.MAX_SEGMENT:
+            raise ValueError("s2_kent_fit: samplesize must be an integer in [2, %d] (a segment is fitted in one workgroup's LDS), got %r"
+                             % (kent.MAX_SEGMENT, S))
+        if labels is not None and (isinstance(coverage_samples, bool) or not isinstance(coverage_samples, int) or coverage_samples < 1):
+            raise ValueError("s2_kent_fit: coverage_samples must be a positive integer, got %r" % (coverage_samples,))
+        dt, dev, batch, data_summary = self._repeat_conditional(conditional_input, S, dtype, device)
+        previous_flags = self.get_embedding_flags()
+        self.set_embedding_flags(True)
+        try:
+            with torch.no_grad():
+                samples = self._obtain_sample(conditional_input=data_summary, predefined_target_input=predefined_base, samplesize=S, seed=seed,
+                                              force_embedding_coordinates=True, dtype=dt, device=dev)[0]
+                assert samples.shape == (batch * S, self.total_target_dim_embedded)
+                a, b = self.target_dim_indices_embedded[k]
+                fit = kent.fit(samples[:, a:b], S)
+                out = {key: fit[key] for key in ("gamma1", "gamma2", "gamma3", "kappa", "u", "loglik", "converged", "num_iter")}
+                if labels is not None:
+                    vec = labels.to(samples)
+                    if vec.shape[1] == 2:
+                        vec = self.layer_list[k][0].spherical_to_eucl_embedding(vec, 0.0)[0]
+                    vec = vec.reshape(batch, 1, 3)
+                    out["label_log_prob"] = kent.log_prob(fit, vec)[:, 0]
+                    out["label_coverage"] = kent.coverage(fit, vec, num_samples=coverage_samples, seed=0 if seed is None else seed)[:, 0]
+        finally:
+            for i, f in enumerate(previous_flags):
+                self.set_embedding_flags(f, sub_pdf_index=i)
+        return {key: _host(v) for key, v in out.items()}
 
     # =========================================================================================== densities on product grids / marginals
     def _target_coordinates(self, force_embedding_coordinates, force_intrinsic_coordinates):
